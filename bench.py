@@ -16,10 +16,17 @@ value = tokens/s of the sharded model (strong scaling: total work fixed), over t
 all-gather transports (RCCL, or the direct-store P2P all-gather when its run passes its self-checks;
 both are in the line).
 
-Extra fields: per-kernel roofline of the dominant kernel (the decode GEMV) from HIP events on
-the launch stream, prefill (N=512, the same sibling groups: one x quantize per group) GB/s and
-int8-MFMA TOP/s, exact-mode decode, the LLaMA-13B / Falcon-7B decode shapes, and the CPU baseline
-(the reference's own ggml.c built from /root/reference into oracle/_ref, on this host's cores).
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does the headline only: it sets up, picks the
+fastest self-checked launch form in a short trial of fixed size, warms up W steps, times N steps of that
+form once, and prints the line.  `--dump-outputs DIR` then writes the last timed step's outputs (the y
+of the last layer's seven mul_mats) as DIR/<name>.npy; the inputs are seeded, so two builds compare
+output for output.
+
+`--full` adds the extra fields: each launch form timed on its own, the persistent-engine decode, the
+per-kernel roofline of the dominant kernel (the decode GEMV) from HIP events on the launch stream,
+prefill (N=512, the same sibling groups: one x quantize per group) GB/s and int8-MFMA TOP/s,
+exact-mode decode, the LLaMA-13B / Falcon-7B decode shapes, the CPU baseline (the reference's own
+ggml.c as built into oracle/_ref, on this host's cores), and with N GPUs the LLaMA-13B sharded line.
 """
 import argparse
 import ctypes
@@ -56,8 +63,18 @@ EXTRA_CONFIGS = [
 ]
 
 
+TRIAL_STEPS, TRIAL_WARMUP = 20, 5    # per launch form and round of the headline's form trial (~25 ms each)
+
+
 def q4_bytes(K, M):
     return 18 * K // 32 * M
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: array} as dirname/<name>.npy, float32 (a few hundred KB in all)"""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def log(*a):
@@ -250,8 +267,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--layers", type=int, default=N_LAYERS)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other leg: each launch form on its own, the engine decode, roofline, "
+                         "prefill, exact mode, the other models' shapes, the CPU baseline, N > 1: the LLaMA-13B sharded "
+                         "line (the --no-* options below trim these legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs (the y of the last layer's mul_mats, float32) as "
+                         "DIR/<name>.npy; the inputs are seeded, so runs with the same arguments compare output for output")
     ap.add_argument("--config4-layers", type=int, default=40,
-                    help="N > 1: layers of the LLaMA-13B row-sharded line (BASELINE config 4); 0 skips it")
+                    help="--full, N > 1: layers of the LLaMA-13B row-sharded line (BASELINE config 4); 0 skips it")
     ap.add_argument("--prefill-tokens", type=int, default=512)
     ap.add_argument("--no-prefill", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
@@ -270,8 +294,9 @@ def main():
                     help="one launch per mul_mat (7 per layer) instead of batching wq/wk/wv and w1/w3")
     ap.add_argument("--decode", choices=("auto", "engine", "launches"), default="auto",
                     help="headline decode path: the persistent LDS-DMA engine (one launch per token, "
-                         "ggml_hip_chain_set_engine), the per-launch graph (4 sibling GEMVs per layer), or auto = "
-                         "the engine when its outputs are bitwise the launches' and it ran faster (both are timed)")
+                         "ggml_hip_chain_set_engine; it must check bitwise against the launches), or the per-launch "
+                         "GEMVs (4 sibling launches per layer); auto = the launches, and --full times the engine beside "
+                         "them (measured slower, DESIGN.md §4c)")
     ap.add_argument("--no-roofline-replays", action="store_true",
                     help="skip the per-position isolated replays of the roofline (profiling runs: the rocprof summary "
                          "then holds the timed replays' GEMVs only)")
@@ -364,9 +389,12 @@ def main():
         b = gh.DeviceBuffer(K * 4 * max(1, args.prefill_tokens))
         gh.check(L.ggml_hip_fill_gaussian(b.ptr, K * max(1, args.prefill_tokens), 0x5EED1000 + K, 0.0, 1.0, None))
         xs[K] = b
-    ys = {M: gh.DeviceBuffer(M * 4 * max(1, args.prefill_tokens)) for M in (4096, 11008)}
-    for K, M in ((4096, 11008), (11008, 4096)):     # prefill: the GEMM's per-call weight image of M rows
-        gh.check(L.ggml_hip_reserve_workspace_mm(K, max(1, args.prefill_tokens), M))
+    do_prefill = args.full and not args.no_prefill and args.prefill_tokens > 0
+    ys = {}
+    if do_prefill:
+        ys = {M: gh.DeviceBuffer(M * 4 * args.prefill_tokens) for M in (4096, 11008)}
+        for K, M in ((4096, 11008), (11008, 4096)):     # prefill: the GEMM's per-call weight image of M rows
+            gh.check(L.ggml_hip_reserve_workspace_mm(K, args.prefill_tokens, M))
     gh.synchronize()
 
     batch = not args.no_batch_siblings
@@ -419,17 +447,18 @@ def main():
         else:
             decode_step()
 
-    def timed(step_fn):
-        for _ in range(args.warmup):
+    def timed(step_fn, steps=None, warmup=None):
+        steps = args.steps if steps is None else steps
+        for _ in range(args.warmup if warmup is None else warmup):
             step_fn()
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(steps):
             step_fn()
         barrier()
         return time.perf_counter() - t0
 
-    # the per-launch chain two ways, interleaved twice, best of each: replayed as one HIP graph per token, and
+    # the per-launch chain two ways: replayed as one HIP graph per token, and
     # issued eagerly from the host (128 launches at ~2.7 us of host time each stay ahead of the ~0.93 ms device
     # step; tools/prefetch_ab.py measured the eager form 1-2 % faster on the device)
     # A third form: the same eager launches through the library's own AQL queue (launch mode 3, ggml-hip-aql.cpp:
@@ -439,14 +468,50 @@ def main():
     profiled = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith("ROCPROF") for k in os.environ)
     aql_ok = hasattr(L, "ggml_hip_debug_set_stream_launch_mode") and not args.eager and not args.no_aql and not profiled
 
-    def timed_aql():                  # the stream's launches through the queue for the whole timed block
+    def timed_aql(**kw):              # the stream's launches through the queue for the whole timed block
         gh.check(L.ggml_hip_debug_set_stream_launch_mode(stream, 3))
         try:
-            return timed(decode_step)
+            return timed(decode_step, **kw)
         finally:
             gh.check(L.ggml_hip_debug_set_stream_launch_mode(stream, 0))
 
+    def outputs():                    # the step's outputs: the y of the last layer's mul_mats
+        return [yb[i].download((LAYER[i][2],), np.float32, stream=stream) for i in range(len(LAYER))]
+
+    run_step()                        # one step of the graph (--eager: of the eager launches): the outputs to match
+    outs_ref = outputs()
+    aql_same = None
+    if aql_ok:                        # bitwise self-check of the AQL form against the graph's outputs
+        for i in range(len(LAYER)):
+            gh.check(L.ggml_hip_memset(yb[i].ptr, 0xFF, LAYER[i][2] * 4, stream))
+        gh.check(L.ggml_hip_debug_set_stream_launch_mode(stream, 3))
+        try:
+            decode_step()
+        finally:
+            gh.check(L.ggml_hip_debug_set_stream_launch_mode(stream, 0))
+        aql_same = all(np.array_equal(o.view(np.uint32), r.view(np.uint32)) for o, r in zip(outputs(), outs_ref))
+    # the headline: the fastest of the forms, picked in a trial of fixed size (the forms interleaved twice, best of
+    # each; its cost does not grow with --steps), then `warmup` + `steps` steps of that form, timed once
+    forms = {}
     if graph is not None:
+        forms["graph"] = lambda **kw: timed(run_step, **kw)
+    forms["eager"] = lambda **kw: timed(decode_step, **kw)
+    if aql_same:
+        forms["aql"] = timed_aql
+    trial = {k: [] for k in forms}
+    if len(forms) > 1:
+        for _ in range(2):
+            for k, f in forms.items():
+                trial[k].append(f(steps=TRIAL_STEPS, warmup=TRIAL_WARMUP))
+    form = min(forms, key=lambda k: min(trial[k])) if len(forms) > 1 else "eager"
+    elapsed_launches = forms[form]()
+    outs_launches = outputs()
+    finite = bool(np.all(np.isfinite(outs_launches[6])))          # the step's last output
+    if not finite:
+        log("WARNING: the decode chain's last output is not finite")
+    # --full: every form on its own, interleaved twice, best of each
+    elapsed_graph = elapsed_eager = elapsed_aql = None
+    if args.full and graph is not None:
         t_graph, t_eager, t_aql = [], [], []
         for _ in range(2):
             t_graph.append(timed(run_step))
@@ -455,48 +520,30 @@ def main():
                 t_aql.append(timed_aql())
         elapsed_graph, elapsed_eager = min(t_graph), min(t_eager)
         elapsed_aql = min(t_aql) if t_aql else None
-        eager_wins = elapsed_eager < elapsed_graph
-        elapsed_launches = min(elapsed_graph, elapsed_eager)
-    else:
-        elapsed_graph, elapsed_eager, eager_wins, elapsed_aql = None, timed(run_step), True, None
-        elapsed_launches = elapsed_eager
-    last = yb[6].download((LAYER[6][2],), np.float32, stream=stream)          # the step's last output
-    finite = bool(np.all(np.isfinite(last)))
-    if not finite:
-        log("WARNING: the decode chain's last output is not finite")
-    outs_launches = [yb[i].download((LAYER[i][2],), np.float32, stream=stream) for i in range(len(LAYER))]
+    elif args.full:
+        elapsed_eager = elapsed_launches
     aql_form = None
-    if elapsed_aql is not None:                # bitwise self-check of the AQL form against the graph's outputs
-        for i in range(len(LAYER)):
-            gh.check(L.ggml_hip_memset(yb[i].ptr, 0xFF, LAYER[i][2] * 4, stream))
-        gh.check(L.ggml_hip_debug_set_stream_launch_mode(stream, 3))
-        try:
-            decode_step()
-        finally:
-            gh.check(L.ggml_hip_debug_set_stream_launch_mode(stream, 0))
-        same = all(np.array_equal(yb[i].download((LAYER[i][2],), np.float32, stream=stream).view(np.uint32),
-                                  outs_launches[i].view(np.uint32)) for i in range(len(LAYER)))
+    if elapsed_aql is not None:
         aql_form = {"tok_s": round(args.steps / elapsed_aql * 32 / args.layers, 2),
-                    "ms_per_step": round(elapsed_aql / args.steps * 1e3, 4), "bitwise_vs_graph": bool(same)}
-        if same and elapsed_aql < elapsed_launches:
-            elapsed_launches = elapsed_aql
-            eager_wins = "aql"
+                    "ms_per_step": round(elapsed_aql / args.steps * 1e3, 4), "bitwise_vs_graph": bool(aql_same)}
     engine = None
-    if args.decode != "launches" and graph is not None and batch:
+    if (args.decode == "engine" or (args.full and args.decode == "auto")) and graph is not None and batch:
         engine = engine_decode(gh, L, launch_args, yb, outs_launches, stream, timed)
         if args.decode == "engine" and not engine.get("on"):
             raise SystemExit(f"--decode engine: the engine declined the chain: {engine.get('declined')}")
-    # the engine is the headline only when asked for, or (auto) when it checked bitwise AND ran faster than the
-    # per-launch graph; round 6 measured it slower (profiles/r06_engine_variants.txt), so auto keeps
-    # the launches and the line carries both
+    # the engine is the headline only when asked for and checked bitwise; round 6 measured it slower than the
+    # per-launch graph (profiles/r06_engine_variants.txt), so auto keeps the launches and the --full
+    # line carries both
     engine_ok = engine is not None and engine.get("on") and engine["bitwise_vs_launches"] and engine["status"] == 0
-    use_engine = engine_ok and (args.decode == "engine" or engine["elapsed_s"] < elapsed_launches)
+    use_engine = engine_ok and args.decode == "engine"
     if engine is not None and engine.get("on"):
         engine["tok_s"] = round(args.steps / engine["elapsed_s"] * 32 / args.layers, 2)
         engine["ms_per_step"] = round(engine["elapsed_s"] / args.steps * 1e3, 4)
     elapsed = engine["elapsed_s"] if use_engine else elapsed_launches
     ms_per_step = elapsed / args.steps * 1e3
     tok_s = args.steps / elapsed * 32 / args.layers if args.layers else 0.0   # per full 32-layer token
+    if args.dump_outputs:             # the engine's outputs are these bit for bit (engine_ok)
+        dump_outputs(args.dump_outputs, {"y_" + LAYER[i][0]: o for i, o in enumerate(outs_launches)})
 
     result = {
         "metric": METRIC, "value": round(tok_s, 2), "unit": "tok/s", "n_gpus": 1, "steps": args.steps,
@@ -515,10 +562,11 @@ def main():
                                    "outputs bitwise the per-launch GEMVs'" if use_engine else
                                    "per-launch GEMVs, " + (
                                        "issued through the library's own AQL queue (launch mode 3; the fastest form here, "
-                                       "bitwise the graph's outputs)" if eager_wins == "aql" else
-                                       "issued eagerly (faster than the per-token HIP graph here)" if eager_wins else
+                                       "bitwise the graph's outputs)" if form == "aql" else
+                                       "issued eagerly (faster than the per-token HIP graph here)" if form == "eager" else
                                        "one HIP graph per token")),
                    "launches_per_layer": 0.0 if use_engine else len(groups),
+                   "form_trial_ms_per_step": {k: round(min(v) / TRIAL_STEPS * 1e3, 4) for k, v in trial.items() if v},
                    "sibling_batching": "wq|wk|wv and w1|w3 share src1 -> one launch each" if batch else "off",
                    "collectives_per_layer": 0, "parallelism": "single GPU", "activations_finite": finite},
     }
@@ -527,26 +575,28 @@ def main():
         result["launches_graph"] = {"tok_s": round(args.steps / elapsed_graph * 32 / args.layers, 2),
                                     "ms_per_step": round(elapsed_graph / args.steps * 1e3, 4),
                                     "launches_per_layer": len(groups)}
-    result["launches_eager"] = {"tok_s": round(args.steps / elapsed_eager * 32 / args.layers, 2),
-                                "ms_per_step": round(elapsed_eager / args.steps * 1e3, 4),
-                                "launches_per_layer": len(groups)}
+    if elapsed_eager is not None:
+        result["launches_eager"] = {"tok_s": round(args.steps / elapsed_eager * 32 / args.layers, 2),
+                                    "ms_per_step": round(elapsed_eager / args.steps * 1e3, 4),
+                                    "launches_per_layer": len(groups)}
     if aql_form is not None:
         result["launches_aql"] = aql_form
     if engine is not None:
         result["engine"] = {k: v for k, v in engine.items() if k != "elapsed_s"}
-    result["roofline"] = kernel_roofline(gh, L, launch_args, xs, stream, len(groups),
-                                         elapsed_launches / args.steps * 1e3, args.layers,
-                                         engine_step_ms=result.get("engine", {}).get("ms_per_step"),
-                                         isolated=not args.no_roofline_replays)
-    if not args.no_prefill and args.prefill_tokens > 0:
+    if args.full:
+        result["roofline"] = kernel_roofline(gh, L, launch_args, xs, stream, len(groups),
+                                             elapsed_launches / args.steps * 1e3, args.layers,
+                                             engine_step_ms=result.get("engine", {}).get("ms_per_step"),
+                                             isolated=not args.no_roofline_replays)
+    if do_prefill:
         result["prefill"] = prefill_bench(gh, L, stack, xs, ys, stream, args.prefill_tokens,
                                           groups=[tuple(g) for g in groups])
-    if not args.no_exact:
+    if args.full and not args.no_exact:
         result["exact_mode"] = exact_decode(gh, L, decode_step, stream, args)
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         result["other_configs"] = [extra_decode(gh, L, stream, *c, steps=args.steps, warmup=args.warmup)
                                    for c in EXTRA_CONFIGS]
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         result["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
     print(json.dumps(result), flush=True)
 
@@ -560,7 +610,7 @@ def sharded_main(gh, L, comm, comm_kind, rank, world, args, stream, allreduce, b
     """N ranks (one process each): every matrix row-sharded N ways (GGML_BACKEND_GPU_SPLIT); per layer 4
     launches (siblings batched) each followed by one grouped all-gather.  The headline is LLaMA-7B (32
     layers) over the faster self-checked transport; the BASELINE config-4 line (LLaMA-13B, 40 layers) rides
-    along.  File comm: the RCCL transport is unavailable (ranks may share a device), P2P only."""
+    along with --full.  File comm: the RCCL transport is unavailable (ranks may share a device), P2P only."""
     use_p2p = comm_kind == "file" or (world > 1 and not args.no_p2p)
     p2p_state = {"on": False, "error": None}
     if use_p2p:
@@ -575,7 +625,9 @@ def sharded_main(gh, L, comm, comm_kind, rank, world, args, stream, allreduce, b
     batch = not args.no_batch_siblings
     groups = [[0, 1, 2], [3], [4, 5], [6]] if batch else [[i] for i in range(len(LAYER))]
     line = sharded_decode(gh, L, comm, comm_kind, rank, world, LAYER, args.layers, groups, args, stream, allreduce,
-                          barrier, p2p_state, 0x5EED0000)
+                          barrier, p2p_state, 0x5EED0000, keep_outputs=bool(args.dump_outputs) and rank == 0)
+    if "outputs" in line:
+        dump_outputs(args.dump_outputs, line.pop("outputs"))
     tok_s, ms = line["tok_s"], line["ms_per_step"]
     result = {
         "metric": METRIC, "value": tok_s, "unit": "tok/s", "n_gpus": world, "steps": args.steps,
@@ -603,7 +655,7 @@ def sharded_main(gh, L, comm, comm_kind, rank, world, args, stream, allreduce, b
         result["config"]["p2p_transport"] = line["transports"]["p2p"]
     if p2p_state["error"]:
         result["config"]["p2p_transport"] = {"error": p2p_state["error"]}
-    if args.config4_layers > 0 and world > 1:
+    if args.full and args.config4_layers > 0 and world > 1:
         c4 = sharded_decode(gh, L, comm, comm_kind, rank, world, LLAMA13B, args.config4_layers, groups, args, stream,
                             allreduce, barrier, p2p_state, 0x5EEF0000, tokens_per=40)
         result["config4_llama13b_sharded"] = dict(
@@ -615,7 +667,7 @@ def sharded_main(gh, L, comm, comm_kind, rank, world, args, stream, allreduce, b
 
 
 def sharded_decode(gh, L, comm, comm_kind, rank, world, spec, n_layers, groups, args, stream, allreduce, barrier,
-                   p2p_state, seed_base, tokens_per=32):
+                   p2p_state, seed_base, tokens_per=32, keep_outputs=False):
     """One model's row-sharded decode: the split graph on each available transport (RCCL, P2P), the same
     shards without collectives (compute only), and the bitwise split self-check.  tok/s per full model
     (`tokens_per` layers), max over ranks of the timed region."""
@@ -734,6 +786,9 @@ def sharded_decode(gh, L, comm, comm_kind, rank, world, spec, n_layers, groups, 
     out["ms_per_step"] = round(best[1] / args.steps * 1e3, 4)
     out["split_check"] = best[2]
     out["self_checks_passed"] = bool(good)
+    if keep_outputs:                         # the gathered y of the last layer's mul_mats, as the last timed step left them
+        out["outputs"] = {"y_" + spec[i][0]: ysplit[i].download((spec[i][2],), np.float32, stream=stream)
+                          for i in range(len(spec))}
     stack.free()
     return out
 

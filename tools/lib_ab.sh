@@ -13,7 +13,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
       echo "$v gemm: $(tr '\n' ' ' < gpurun_out/ab/gemm_$v.$r.log)"
     fi
     if [ -z "$NO_GEMV" ]; then
-      GGML_HIP_LIB=$lib timeout -k 10 240 python bench.py --steps 20 --warmup 3 --no-cpu --no-prefill --no-exact --no-extra \
+      GGML_HIP_LIB=$lib timeout -k 10 240 python bench.py --full --steps 20 --warmup 3 --no-cpu --no-prefill --no-exact --no-extra \
           > gpurun_out/ab/bench_$v.$r.log 2>&1 || { echo "bench $v rc=$?"; exit 1; }
       python - "$v" gpurun_out/ab/bench_$v.$r.log <<'PY'
 import json, sys

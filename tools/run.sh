@@ -27,12 +27,12 @@ if has tests; then
 fi
 has smoke && step smoke 180 python -c "import __graft_entry__ as g; g.smoke()"
 if has bench; then
-  step bench 480 python bench.py ${BENCH_ARGS:-}
+  step bench 480 python bench.py --full ${BENCH_ARGS:-}
   tail -1 "$O/bench.log" | cut -c1-400
 fi
 if has prof; then    # the bench's own timed replays under the kernel tracer
   step prof 300 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run --output-format csv -- \
-      python3 bench.py --steps 20 --warmup 5 --no-cpu --no-extra --no-exact --no-roofline-replays --no-aql ${BENCH_ARGS:-}
+      python3 bench.py --full --steps 20 --warmup 5 --no-cpu --no-extra --no-exact --no-roofline-replays --no-aql ${BENCH_ARGS:-}
   tail -1 "$O/prof.log" | cut -c1-300
   python3 tools/trace_steps.py "$O/prof" "$O/prof.log" > "$O/step_spans.json" || true
 fi
@@ -40,11 +40,11 @@ if has final; then   # round-end evidence: the traced run first, installed under
   # bench, whose roofline.rocprof_check reads those files: the line and the committed profiles agree
   R=${ROUND:-r06}
   step prof 300 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run --output-format csv -- \
-      python3 bench.py --steps 20 --warmup 5 --no-cpu --no-extra --no-exact --no-roofline-replays --no-aql
+      python3 bench.py --full --steps 20 --warmup 5 --no-cpu --no-extra --no-exact --no-roofline-replays --no-aql
   python3 tools/trace_steps.py "$O/prof" "$O/prof.log" > "$O/step_spans.json"
   cp "$O/prof/run_kernel_stats.csv" "profiles/${R}_bench_rocprofv3_kernel_stats.csv"
   cp "$O/step_spans.json" "profiles/${R}_bench_rocprofv3_step_spans.json"
-  step bench 480 python bench.py
+  step bench 480 python bench.py --full
   tail -1 "$O/bench.log" | cut -c1-400
 fi
 if has pmc; then     # decode GEMV HBM bytes: one counter per pass (gfx950: FETCH_SIZE is half the streamed bytes)
