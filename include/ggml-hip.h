@@ -7,7 +7,10 @@
  * INTEGRATION.md).  Plain pointers and sizes only; no torch types.
  *
  * Scope: GGML_OP_MUL_MAT with src0 = GGML_TYPE_Q4_0, src1 = dst = GGML_TYPE_F32
- * (the path BASELINE.json names).  Everything else returns "cannot" so ggml's
+ * (the path BASELINE.json names), and the same with src0 = GGML_TYPE_Q6_K: the
+ * output.weight a k-quants build's quantizer writes into every q4_0 file
+ * (llama.cpp:2416-2421; ggml_vec_dot_q6_K_q8_K semantics, k_quants.c).  Everything
+ * else, the other k-quant types included, returns "cannot" so ggml's
  * CPU path runs, exactly as ggml_cuda_can_mul_mat / ggml_cuda_compute_forward
  * return false for what they do not handle.
  *
@@ -144,6 +147,24 @@ int ggml_hip_mul_mat_q4_0(const void *dev_w, int64_t K, int64_t M, const float *
  * ggml_vec_dot_q4_0_q8_0 (ggml.c:2412-2435; same q8_0 bytes, same fp32 fma schedule). */
 int ggml_hip_mul_mat_q4_0_ex(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N,
                              float *dev_y, int64_t ldy, int algo, void *stream);
+/* Q6_K weights (block_q6_K rows, 210 bytes per 256 weights, 2-byte aligned) x F32 -> F32 with the semantics of
+ * the reference's CPU path (k_quants.c, QK_K = 256).  Stream-ordered and graph-capturable: no allocation in a
+ * call once the workspace is reserved (ggml_hip_reserve_workspace(K, N) covers the exact mode's q8_K of x).
+ * Status codes as for the q4_0 entry points; K % 256 != 0 -> GGML_HIP_ERR_INVALID.
+ * The kernels read the Q6_K rows as naturally aligned 32-bit words, so up to 2 bytes below dev_w (when it sits at
+ * 2 mod 4) and up to 2 bytes past the last row (when it ends at 2 mod 4) are read and ignored: the matrix must lie
+ * in an allocation whose first and last aligned 4-byte words are readable (any hipMalloc'ed buffer).
+ * quantize_q8_K: N rows of K f32 -> block_q8_K (292 bytes per 256), bit-exact to quantize_row_q8_K_reference
+ * (k_quants.c:1133-1168); bsums of an all-zero block are written as zeros (the reference leaves them unwritten). */
+int ggml_hip_quantize_q8_K(const float *dev_x, int64_t K, int64_t N, void *dev_xq, void *stream);
+/* dequantize_row_q6_K (k_quants.c:1065-1110), bit-exact. */
+int ggml_hip_dequantize_q6_K(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream);
+/* y[n*ldy + m] = W[m] . x[n].  algo: 0 auto (4 in exact mode, else 1), 1 GEMV with the q8_K quantization of x
+ * fused in (K <= 16384; column tiles of 8 for N > 8, bitwise the per-tile calls), 4 exact: bit-identical to the
+ * AVX2 branch of ggml_vec_dot_q6_K_q8_K (k_quants.c:3484-3561). */
+int ggml_hip_mul_mat_q6_K(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N,
+                          float *dev_y, int64_t ldy, int algo, void *stream);
+
 /* Sibling mul_mats that share the activation x (ggml graphs issue wq/wk/wv and w1/w3 on the same
  * src1): n <= 4 weight matrices of the same K, y_i = W_i x with y_i f32 [N][M_i].  One launch for
  * N <= 8 (rows concatenated); for N > 8 x is quantized once and each W_i runs the GEMM.  Results

@@ -41,6 +41,28 @@ int ggml_hip_mul_mat_q4_0_ex(const void *dev_w, int64_t K, int64_t M, const floa
     return mul_mat_dev(dev_w, K, M, dev_x, N, dev_y, ldy, algo, resolve_stream(stream));
 }
 
+int ggml_hip_quantize_q8_K(const float *dev_x, int64_t K, int64_t N, void *dev_xq, void *stream) {
+    if (!dev_x || !dev_xq || K <= 0 || K % QK_K || N < 0) return fail(GGML_HIP_ERR_INVALID, "bad arguments");
+    if (!aligned(dev_x, 16) || !aligned(dev_xq, 4))
+        return fail(GGML_HIP_ERR_INVALID, "x must be 16-byte aligned, the q8_K rows 4-byte aligned");
+    HIP_RET(ghip::quantize_q8_K(dev_x, K, N, dev_xq, resolve_stream(stream)));
+    return GGML_HIP_OK;
+}
+
+int ggml_hip_dequantize_q6_K(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
+    if (!dev_w || !dev_wq || K <= 0 || K % QK_K || M < 0) return fail(GGML_HIP_ERR_INVALID, "bad arguments");
+    if (!aligned(dev_wq, 2) || !aligned(dev_w, 16))
+        return fail(GGML_HIP_ERR_INVALID, "w must be 16-byte aligned, the Q6_K rows 2-byte aligned");
+    HIP_RET(ghip::dequantize_q6_K(dev_wq, K, M, dev_w, resolve_stream(stream)));
+    return GGML_HIP_OK;
+}
+
+int ggml_hip_mul_mat_q6_K(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N, float *dev_y,
+                          int64_t ldy, int algo, void *stream) {
+    ensure_init();
+    return mul_mat_q6k_dev(dev_w, K, M, dev_x, N, dev_y, ldy, algo, resolve_stream(stream));
+}
+
 int ggml_hip_mul_mat_q4_0_multi(int n, const void *const *dev_w, const int64_t *M, int64_t K, const float *dev_x,
                                 int64_t N, float *const *dev_y, void *stream) {
     ensure_init();

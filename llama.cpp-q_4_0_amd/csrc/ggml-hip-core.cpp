@@ -293,6 +293,36 @@ int mul_mat_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, 
     return GGML_HIP_OK;
 }
 
+// The Q6_K mul_mat (q6_k.hip): the fused GEMV at every N (column tiles of 8), or in exact mode the q8_K
+// quantizer into the stream's workspace and the exact kernel.  An MFMA prefill GEMM is a follow-up.
+size_t workspace_bytes_q8k(int64_t K, int64_t N) { return (size_t)N * (size_t)(K / QK_K) * Q8KB; }
+
+int mul_mat_q6k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                    hipStream_t s) {
+    if (!w || !x || !y || K <= 0 || M <= 0 || N < 0) return fail(GGML_HIP_ERR_INVALID, "null pointer or bad shape");
+    if (K % QK_K != 0) return fail(GGML_HIP_ERR_INVALID, "K must be a multiple of 256 (QK_K)");
+    if (N == 0) return GGML_HIP_OK;
+    if (ldy < M) return fail(GGML_HIP_ERR_INVALID, "ldy < M");
+    if (!aligned(w, 2) || !aligned(x, 16) || !aligned(y, 4))
+        return fail(GGML_HIP_ERR_INVALID, "W must be 2-byte, x 16-byte, y 4-byte aligned");
+    if (M >= ((int64_t)1 << 31) || N * K >= ((int64_t)1 << 31))
+        return fail(GGML_HIP_ERR_UNSUPPORTED, "matrix too large for 32-bit indices; split rows or columns");
+    const int id = current_device();
+    if (algo == 0) algo = exact_mode() ? 4 : 1;
+    if (algo == 1) {
+        if (K > 16384) return fail(GGML_HIP_ERR_UNSUPPORTED, "the Q6_K GEMV supports K <= 16384");
+        HIP_RET(ghip::gemv_q6_K(w, K, M, x, N, y, ldy, g_dev[id].info, s));
+        return GGML_HIP_OK;
+    }
+    if (algo != 4) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1 or 4");
+    void *ws = nullptr;
+    const int wrc = stream_workspace(id, s, workspace_bytes_q8k(K, N), &ws);
+    if (wrc != GGML_HIP_OK) return wrc;
+    HIP_RET(ghip::quantize_q8_K(x, K, N, ws, s));
+    HIP_RET(ghip::mm_exact_q6_K(w, K, M, ws, N, y, ldy, s));
+    return GGML_HIP_OK;
+}
+
 // Sibling matrices (one x) that all take k_gemm9 on a registered fp6 image: ONE launch over their
 // row tiles (the x image built once, as before).  The launch plans its tiles (128 x 128 / 128 x 64 /
 // mixed, half tiles) from its own total tile count, which can differ from the per-matrix launches'
@@ -355,6 +385,15 @@ void split_range(int64_t nrows, int id, int64_t *lo, int64_t *hi) {
 bool supported_mul_mat(const tensor *src0, const tensor *src1, const tensor *dst) {
     return src0 && src1 && dst && src0->type == gabi::TYPE_Q4_0 && src1->type == gabi::TYPE_F32 &&
            dst->type == gabi::TYPE_F32 && src0->ne[0] % 64 == 0 && src0->ne[0] == src1->ne[0] &&
+           dst->ne[0] == src0->ne[1] && dst->ne[1] == src1->ne[1] && src0->ne[2] == src1->ne[2] &&
+           src0->ne[3] == src1->ne[3] && is_contiguous(src0) && is_contiguous(src1) && is_contiguous(dst);
+}
+
+// contiguous Q6_K x F32 -> F32 (a k-quants model's output.weight); kept apart from supported_mul_mat, which
+// gates everything q4_0-only: the q4_0 kernels, weight images, sibling groups, chains and the engine
+bool supported_mul_mat_q6k(const tensor *src0, const tensor *src1, const tensor *dst) {
+    return src0 && src1 && dst && src0->type == gabi::TYPE_Q6_K && src1->type == gabi::TYPE_F32 &&
+           dst->type == gabi::TYPE_F32 && src0->ne[0] > 0 && src0->ne[0] % QK_K == 0 && src0->ne[0] == src1->ne[0] &&
            dst->ne[0] == src0->ne[1] && dst->ne[1] == src1->ne[1] && src0->ne[2] == src1->ne[2] &&
            src0->ne[3] == src1->ne[3] && is_contiguous(src0) && is_contiguous(src1) && is_contiguous(dst);
 }

@@ -80,6 +80,9 @@ using gabi::tensor;
 
 constexpr int QK = 32;
 constexpr int Q4B = 18;
+using ghip::QK_K;             // k-quants superblock and block sizes (q4_0_kernels.h)
+using ghip::Q6KB;
+using ghip::Q8KB;
 
 extern thread_local std::string g_last_error;
 int fail(int code, const std::string &msg);
@@ -153,6 +156,10 @@ int mul_mat_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, 
                 hipStream_t s, unsigned *xq = nullptr);
 int mul_mat_group_g9(int n, const void *const *w, const int64_t *M, int64_t K, const float *x, int64_t N,
                      float *const *y, hipStream_t s);
+// the Q6_K mul_mat: algo 0 auto (4 in exact mode, else 1), 1 GEMV (column tiles of 8), 4 exact
+size_t workspace_bytes_q8k(int64_t K, int64_t N);
+int mul_mat_q6k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                    hipStream_t s);
 // true when ggml_hip_mul_mat_q4_0_multi runs these n siblings at N tokens as ONE k_gemm9 launch on registered
 // fp6 images (mul_mat_group_g9 for n > 1, mul_mat_dev's image GEMM for n = 1); img[i] = the images
 bool g9_images(int n, const void *const *w, const int64_t *M, int64_t K, int64_t N, const void **img);
@@ -162,6 +169,7 @@ bool is_contiguous(const tensor *t);
 bool on_device(const tensor *t);
 void split_range(int64_t nrows, int id, int64_t *lo, int64_t *hi);
 bool supported_mul_mat(const tensor *src0, const tensor *src1, const tensor *dst);
+bool supported_mul_mat_q6k(const tensor *src0, const tensor *src1, const tensor *dst);
 [[noreturn]] void op_abort(const tensor *t, const char *why);
 inline bool same_shape(const tensor *a, const tensor *b) {
     return a->ne[0] == b->ne[0] && a->ne[1] == b->ne[1] && a->ne[2] == b->ne[2] && a->ne[3] == b->ne[3];

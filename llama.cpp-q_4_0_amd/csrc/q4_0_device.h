@@ -113,6 +113,7 @@ constexpr int DPP_ROW_HALF_MIRROR = 0x141;
 constexpr int DPP_ROW_MIRROR = 0x140;
 constexpr int DPP_ROW_BCAST15 = 0x142;
 constexpr int DPP_ROW_BCAST31 = 0x143;
+constexpr int DPP_WAVE_SHL1 = 0x130;    // lane l reads lane l + 1 (lane 63: 0)
 
 // max / sum over each group of 8 consecutive lanes (every lane of the group gets the result)
 __device__ __forceinline__ float group8_max(float v) {
@@ -133,6 +134,21 @@ __device__ __forceinline__ float wave_sum_lane63(float v) {
     v += dpp_f<DPP_ROW_MIRROR>(v);
     v += dpp_f<DPP_ROW_BCAST15, 0xA>(v);
     v += dpp_f<DPP_ROW_BCAST31, 0xC>(v);
+    return v;
+}
+
+// the same for int32 (exact, any order): the total is valid in lane 63
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ int dpp_im(int v) {          // lanes outside ROW_MASK read 0
+    return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xF, false);
+}
+__device__ __forceinline__ int wave_isum_lane63(int v) {
+    v += dpp_i<DPP_QUAD_XOR1>(v);
+    v += dpp_i<DPP_QUAD_XOR2>(v);
+    v += dpp_i<DPP_ROW_HALF_MIRROR>(v);
+    v += dpp_i<DPP_ROW_MIRROR>(v);
+    v += dpp_im<DPP_ROW_BCAST15, 0xA>(v);
+    v += dpp_im<DPP_ROW_BCAST31, 0xC>(v);
     return v;
 }
 

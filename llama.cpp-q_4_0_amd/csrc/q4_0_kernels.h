@@ -133,6 +133,21 @@ hipError_t mm_exact_q4_0(const void *W, int64_t K, int64_t M, const int8_t *xqs,
 hipError_t mm_exact_q4_0_multi(int n, const void *const *W, const int64_t *M, int64_t K, const int8_t *xqs,
                                const float *xd, int64_t N, float *const *y, const int64_t *ldy, hipStream_t s);
 
+// Q6_K (q6_k.hip): the output.weight of a k-quants q4_0 model.  W: ggml block_q6_K rows, verbatim
+// (210 bytes per 256 weights, rows only 2-byte aligned); xq8k: ggml block_q8_K rows (292 bytes per 256).
+constexpr int QK_K = 256;     // k-quants superblock
+constexpr int Q6KB = 210;     // sizeof(block_q6_K)
+constexpr int Q8KB = 292;     // sizeof(block_q8_K)
+// quantize_row_q8_K_reference / dequantize_row_q6_K, bit-exact
+hipError_t quantize_q8_K(const float *x, int64_t K, int64_t N, void *xq8k, hipStream_t s);
+hipError_t dequantize_q6_K(const void *wq, int64_t K, int64_t M, float *w, hipStream_t s);
+// fused q8_K quantize of x (LDS) + q6_K.q8_K GEMV; K % 256 == 0, K <= 16384; N > 8 runs column tiles of 8
+hipError_t gemv_q6_K(const void *W, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
+                     const DeviceInfo &dev, hipStream_t s);
+// exact mode: y bit-identical to the AVX2 ggml_vec_dot_q6_K_q8_K on the pre-quantized xq8k; any N
+hipError_t mm_exact_q6_K(const void *W, int64_t K, int64_t M, const void *xq8k, int64_t N, float *y, int64_t ldy,
+                         hipStream_t s);
+
 // Multi-GPU helper: y[n*ldy + row0[r] + i] = slab[r][n][i] for i < rows[r] (gather compaction).
 // row_begin travels as a kernel argument (no host->device copy, capture-safe)
 static constexpr int SCATTER_MAX_RANKS = 256;

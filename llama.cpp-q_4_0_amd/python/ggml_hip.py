@@ -55,6 +55,9 @@ def _bind(L):
         "ggml_hip_dequantize_q4_0": ([vp, i64, i64, vp, vp], i32),
         "ggml_hip_mul_mat_q4_0": ([vp, i64, i64, vp, i64, vp, vp], i32),
         "ggml_hip_mul_mat_q4_0_ex": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
+        "ggml_hip_quantize_q8_K": ([vp, i64, i64, vp, vp], i32),
+        "ggml_hip_dequantize_q6_K": ([vp, i64, i64, vp, vp], i32),
+        "ggml_hip_mul_mat_q6_K": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
         "ggml_hip_reserve_workspace": ([i64, i64], i32),
         "ggml_hip_reserve_workspace_mm": ([i64, i64, i64], i32),
         "ggml_hip_weight_image_create": ([vp, i64, i64, vp], i32),
@@ -248,6 +251,20 @@ def mul_mat_multi(ws, Ms, K, x_dev, N, ys, stream=None):
     check(load().ggml_hip_mul_mat_q4_0_multi(n, wp, mp, K, xp, N, yp, stream), "mul_mat_q4_0_multi")
 
 
+def quantize_q8_K(x_dev, K, N, xq_dev, stream=None):
+    check(load().ggml_hip_quantize_q8_K(_ptr(x_dev), K, N, _ptr(xq_dev), stream), "quantize_q8_K")
+
+
+def dequantize_q6_K(wq_dev, K, M, w_dev, stream=None):
+    check(load().ggml_hip_dequantize_q6_K(_ptr(wq_dev), K, M, _ptr(w_dev), stream), "dequantize_q6_K")
+
+
+def mul_mat_q6_K(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_off=0, x_off=0, y_off=0):
+    """Q6_K rows (210 * K / 256 bytes each) x f32 [N][K] -> f32 y[n * ldy + m]; algo 0 auto, 1 GEMV, 4 exact."""
+    check(load().ggml_hip_mul_mat_q6_K(_ptr(w_dev) + w_off, K, M, _ptr(x_dev) + x_off, N, _ptr(y_dev) + y_off,
+                                       M if ldy is None else ldy, algo, stream), "mul_mat_q6_K")
+
+
 class ChainTask(ctypes.Structure):
     """struct ggml_hip_chain_task (include/ggml-hip.h)"""
     _fields_ = [("nmat", ctypes.c_int), ("K", ctypes.c_int64), ("x", ctypes.c_void_p),
@@ -359,6 +376,7 @@ class Graph:
 # ggml_tensor mirror (ggml.h:378-414) for driving the tensor ABI from tests
 
 GGML_TYPE_F32, GGML_TYPE_Q4_0 = 0, 2
+GGML_TYPE_Q6_K = 14
 GGML_BACKEND_CPU, GGML_BACKEND_GPU, GGML_BACKEND_GPU_SPLIT = 0, 10, 20
 GGML_OP_MUL_MAT = 32
 GGML_TASK_INIT, GGML_TASK_COMPUTE, GGML_TASK_FINALIZE = 0, 1, 2
@@ -396,6 +414,9 @@ def make_tensor(gtype, ne, data=None, backend=GGML_BACKEND_CPU):
     if gtype == GGML_TYPE_Q4_0:
         t.nb[0] = 18
         t.nb[1] = 18 * ne[0] // 32
+    elif gtype == GGML_TYPE_Q6_K:
+        t.nb[0] = 210
+        t.nb[1] = 210 * ne[0] // 256
     else:
         t.nb[0] = 4
         t.nb[1] = 4 * ne[0]
