@@ -149,7 +149,8 @@ int ggml_hip_mul_mat_q4_0_ex(const void *dev_w, int64_t K, int64_t M, const floa
                              float *dev_y, int64_t ldy, int algo, void *stream);
 /* Q6_K weights (block_q6_K rows, 210 bytes per 256 weights, 2-byte aligned) x F32 -> F32 with the semantics of
  * the reference's CPU path (k_quants.c, QK_K = 256).  Stream-ordered and graph-capturable: no allocation in a
- * call once the workspace is reserved (ggml_hip_reserve_workspace(K, N) covers the exact mode's q8_K of x).
+ * call once the workspace is reserved (ggml_hip_reserve_workspace(K, N) covers the exact mode's q8_K of x and the
+ * prefill GEMM's q8_K planes).
  * Status codes as for the q4_0 entry points; K % 256 != 0 -> GGML_HIP_ERR_INVALID.
  * The kernels read the Q6_K rows as naturally aligned 32-bit words, so up to 2 bytes below dev_w (when it sits at
  * 2 mod 4) and up to 2 bytes past the last row (when it ends at 2 mod 4) are read and ignored: the matrix must lie
@@ -159,11 +160,19 @@ int ggml_hip_mul_mat_q4_0_ex(const void *dev_w, int64_t K, int64_t M, const floa
 int ggml_hip_quantize_q8_K(const float *dev_x, int64_t K, int64_t N, void *dev_xq, void *stream);
 /* dequantize_row_q6_K (k_quants.c:1065-1110), bit-exact. */
 int ggml_hip_dequantize_q6_K(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream);
-/* y[n*ldy + m] = W[m] . x[n].  algo: 0 auto (4 in exact mode, else 1), 1 GEMV with the q8_K quantization of x
- * fused in (K <= 16384; column tiles of 8 for N > 8, bitwise the per-tile calls), 4 exact: bit-identical to the
- * AVX2 branch of ggml_vec_dot_q6_K_q8_K (k_quants.c:3484-3561). */
+/* y[n*ldy + m] = W[m] . x[n].  algo: 0 auto (4 in exact mode; else 5 when N >= the GEMM threshold or K > 16384;
+ * else 1), 1 GEMV with the q8_K quantization of x fused in (K <= 16384; column tiles of 8 for N > 8, bitwise the
+ * per-tile calls), 4 exact: bit-identical to the AVX2 branch of ggml_vec_dot_q6_K_q8_K (k_quants.c:3484-3561),
+ * 5 prefill GEMM on the int8 matrix cores (any K % 256 == 0): the Q6_K bytes read in place, x quantized to q8_K
+ * into the workspace; every y bit for bit algo 1's (the same exact integer superblock sums and the same fp32
+ * step per superblock, in order), so the auto switch between 1 and 5 never changes a result.  2 and 3 are invalid. */
 int ggml_hip_mul_mat_q6_K(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N,
                           float *dev_y, int64_t ldy, int algo, void *stream);
+/* debug, no device needed: the algo that algo 0 of ggml_hip_mul_mat_q6_K would run now: 1, 4 or 5 */
+int ggml_hip_debug_q6k_auto_algo(int64_t K, int64_t M, int64_t N);
+/* debug: the smallest N at which auto takes the GEMM (default: the measured crossover; GGML_HIP_Q6K_GEMM_MIN_N;
+ * values below 9 count as 9); -1 restores the environment value or the default.  Returns the previous value. */
+int ggml_hip_debug_set_q6k_gemm_min_n(int n);
 
 /* Sibling mul_mats that share the activation x (ggml graphs issue wq/wk/wv and w1/w3 on the same
  * src1): n <= 4 weight matrices of the same K, y_i = W_i x with y_i f32 [N][M_i].  One launch for

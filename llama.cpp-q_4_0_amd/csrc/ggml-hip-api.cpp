@@ -63,6 +63,13 @@ int ggml_hip_mul_mat_q6_K(const void *dev_w, int64_t K, int64_t M, const float *
     return mul_mat_q6k_dev(dev_w, K, M, dev_x, N, dev_y, ldy, algo, resolve_stream(stream));
 }
 
+int ggml_hip_debug_q6k_auto_algo(int64_t K, int64_t M, int64_t N) {
+    if (K <= 0 || K % QK_K || M <= 0 || N < 0) return fail(GGML_HIP_ERR_INVALID, "bad shape");
+    return q6k_auto_algo(K, M, N);
+}
+
+int ggml_hip_debug_set_q6k_gemm_min_n(int n) { return q6k_set_gemm_min_n(n); }
+
 int ggml_hip_mul_mat_q4_0_multi(int n, const void *const *dev_w, const int64_t *M, int64_t K, const float *dev_x,
                                 int64_t N, float *const *dev_y, void *stream) {
     ensure_init();

@@ -293,9 +293,43 @@ int mul_mat_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, 
     return GGML_HIP_OK;
 }
 
-// The Q6_K mul_mat (q6_k.hip): the fused GEMV at every N (column tiles of 8), or in exact mode the q8_K
-// quantizer into the stream's workspace and the exact kernel.  An MFMA prefill GEMM is a follow-up.
+// The Q6_K mul_mat (q6_k.hip, q6_k_gemm.hip).  Decode: the fused GEMV (column tiles of 8 above N = 8).  Prefill:
+// the q8_K values of x as planes in the stream's workspace and the int8-MFMA GEMM k_gemm_q6_K, whose y is bit
+// for bit the GEMV's (the same exact integer superblock sums, the same fp32 step per superblock in the same
+// order), so the switch between the two never changes a result.  Exact mode: the q8_K quantizer into the
+// workspace and the exact kernel.  Auto takes the GEMM from N >= q6k_gemm_min_n() (measured crossover,
+// tools/q6k_gemm_bench.py; GGML_HIP_Q6K_GEMM_MIN_N / ggml_hip_debug_set_q6k_gemm_min_n, never
+// below 9) and wherever the GEMV cannot run (K > 16384).
 size_t workspace_bytes_q8k(int64_t K, int64_t N) { return (size_t)N * (size_t)(K / QK_K) * Q8KB; }
+// qs int8 [N][K] + d f32 [N][K / 256]; never more than workspace_bytes(K, N), which ggml_hip_reserve_workspace reserves
+size_t workspace_bytes_q6k_gemm(int64_t K, int64_t N) {
+    return ((size_t)(N * K + 255) & ~(size_t)255) + (size_t)N * (size_t)(K / QK_K) * 4;
+}
+
+// the sweep (profiles/q6k_gemm.json, lm_head shape): the GEMM wins at every swept N from 9, the rule's floor
+static constexpr int Q6K_GEMM_MIN_N = 9;
+static constexpr int Q6K_GEMV_MAX_K = 16384;
+std::atomic<int> g_q6k_min_n{-1};
+int q6k_gemm_min_n() {
+    int v = g_q6k_min_n.load(std::memory_order_relaxed);
+    if (v < 0) {
+        const char *e = getenv("GGML_HIP_Q6K_GEMM_MIN_N");
+        int want = e ? atoi(e) : Q6K_GEMM_MIN_N, expect = -1;
+        if (want < 9) want = 9;
+        g_q6k_min_n.compare_exchange_strong(expect, want);
+        v = g_q6k_min_n.load(std::memory_order_relaxed);
+    }
+    return v;
+}
+int q6k_set_gemm_min_n(int n) {
+    const int prev = q6k_gemm_min_n();
+    g_q6k_min_n.store(n < 0 ? -1 : (n < 9 ? 9 : n), std::memory_order_relaxed);     // -1: re-read the environment
+    return prev;
+}
+int q6k_auto_algo(int64_t K, int64_t, int64_t N) {
+    if (exact_mode()) return 4;
+    return (N >= q6k_gemm_min_n() || K > Q6K_GEMV_MAX_K) ? 5 : 1;
+}
 
 int mul_mat_q6k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
                     hipStream_t s) {
@@ -308,14 +342,24 @@ int mul_mat_q6k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t
     if (M >= ((int64_t)1 << 31) || N * K >= ((int64_t)1 << 31))
         return fail(GGML_HIP_ERR_UNSUPPORTED, "matrix too large for 32-bit indices; split rows or columns");
     const int id = current_device();
-    if (algo == 0) algo = exact_mode() ? 4 : 1;
+    if (algo == 0) algo = q6k_auto_algo(K, M, N);
     if (algo == 1) {
-        if (K > 16384) return fail(GGML_HIP_ERR_UNSUPPORTED, "the Q6_K GEMV supports K <= 16384");
+        if (K > Q6K_GEMV_MAX_K) return fail(GGML_HIP_ERR_UNSUPPORTED, "the Q6_K GEMV supports K <= 16384");
         HIP_RET(ghip::gemv_q6_K(w, K, M, x, N, y, ldy, g_dev[id].info, s));
         return GGML_HIP_OK;
     }
-    if (algo != 4) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1 or 4");
+    if (algo != 4 && algo != 5) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1, 4 or 5");
     void *ws = nullptr;
+    if (algo == 5) {
+        if (((M + 63) / 64) * ((N + 63) / 64) >= ((int64_t)1 << 31))
+            return fail(GGML_HIP_ERR_UNSUPPORTED, "too many tiles for one grid; split rows or columns");
+        const int wrc = stream_workspace(id, s, workspace_bytes_q6k_gemm(K, N), &ws);
+        if (wrc != GGML_HIP_OK) return wrc;
+        float *xd = (float *)((char *)ws + ((size_t)(N * K + 255) & ~(size_t)255));
+        HIP_RET(ghip::quantize_q8_K_planes(x, K, N, ws, xd, s));
+        HIP_RET(ghip::gemm_q6_K(w, K, M, ws, xd, N, y, ldy, s));
+        return GGML_HIP_OK;
+    }
     const int wrc = stream_workspace(id, s, workspace_bytes_q8k(K, N), &ws);
     if (wrc != GGML_HIP_OK) return wrc;
     HIP_RET(ghip::quantize_q8_K(x, K, N, ws, s));

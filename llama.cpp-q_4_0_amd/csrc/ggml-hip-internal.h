@@ -156,8 +156,12 @@ int mul_mat_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, 
                 hipStream_t s, unsigned *xq = nullptr);
 int mul_mat_group_g9(int n, const void *const *w, const int64_t *M, int64_t K, const float *x, int64_t N,
                      float *const *y, hipStream_t s);
-// the Q6_K mul_mat: algo 0 auto (4 in exact mode, else 1), 1 GEMV (column tiles of 8), 4 exact
+// the Q6_K mul_mat: algo 0 auto (q6k_auto_algo), 1 GEMV (column tiles of 8), 4 exact, 5 int8-MFMA GEMM
 size_t workspace_bytes_q8k(int64_t K, int64_t N);
+size_t workspace_bytes_q6k_gemm(int64_t K, int64_t N);
+int q6k_auto_algo(int64_t K, int64_t M, int64_t N);     // what algo 0 runs now: 1, 4 or 5 (no device needed)
+int q6k_gemm_min_n();
+int q6k_set_gemm_min_n(int n);                          // -1: the environment value or the default; returns the previous
 int mul_mat_q6k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
                     hipStream_t s);
 // true when ggml_hip_mul_mat_q4_0_multi runs these n siblings at N tokens as ONE k_gemm9 launch on registered

@@ -1,0 +1,268 @@
+// q6_k_gemm.hip — the prefill GEMM of the Q6_K x F32 mul_mat (gfx950, wave64): k_gemm_q6_K on the int8 matrix
+// cores (v_mfma_i32_32x32x32_i8), y bit for bit what the GEMV k_gemv_q6_K (q6_k.hip) gives.
+//
+// The GEMV computes, per output and superblock b of 256 elements, the exact int32
+//   isum_b = sum_g sc[g] sum_(e in g) (q_e - 32) q8_e,   |isum_b| <= 2^27,
+// and then acc = fmaf(d_x[n][b] * d_w[m][b], (float)isum_b, acc), superblocks in order from +0: ONE fp32 step per
+// 256 weights.  Q6_K's scales are integers, so the scaled weight w' = sc (q - 32) is an integer in
+// [-4064, 4096] and splits exactly into two int8 digits, w' = 128 hi + lo with lo in [-64, 63], hi in [-32, 32].
+// Two MFMA chains over the superblock's K = 256, hi . q8 and lo . q8, accumulate H (|H| <= 2^20) and
+// L (|L| <= 2^21) in int32 with nothing in between; isum_b = 128 H + L exactly, and the fp32 step that follows
+// is the GEMV's, in the GEMV's order (K is never split across waves or workgroups).  Hence equality, not a
+// tolerance, and a result that does not depend on the tile shape or the grid.
+//
+// Weights are read in place (no image): the workgroup decodes its 64-row tile's superblock into the two digit
+// planes in LDS once, and every column of the tile reuses it.  The block fields are fetched as in the GEMV: the
+// 53 naturally aligned dwords that hold a 210-byte block are one coalesced load per wave, a wave shift and
+// v_alignbyte_b32 realign a block at 2 mod 4, three ds_bpermute_b32 hand lane t the ql / qh / scale of its
+// elements 4t .. 4t + 3.  Rows >= M and columns >= N of a ragged tile read the last row / column (inside the
+// operands) and are never stored.  x is the q8_K quantization (q8k_block_lane, the GEMV prologue's bits) written
+// as planes: qs int8 [N][K] and d f32 [N][K / 256] (k_quantize_q8_K_planes), so that a column's superblock is
+// sixteen aligned 16-byte loads.
+//
+// Tile: 64 rows x 32 WN TN columns, 2 x WN waves, each TN 32 x 32 MFMA tiles with their H and L ((WN, TN) =
+// (2, 1) up to N = 64, (4, 1) up to 128, else (4, 2): the wider the tile, the more columns share one decode of
+// the weights); MFMA A = x (D's register index = column), B = weights (D's lane = row): a lane's 16 accumulator
+// registers are 16 columns of ONE row, so d_w is one value per lane and the y stores run along m.  LDS rows are
+// 256 + 16 bytes, which spreads the 32 rows of an operand read (16 bytes per lane) over all banks.  One superblock
+// per stage in a single LDS buffer; the next superblock's global loads are issued before the current one's MFMAs.
+#include "q6_k_device.h"
+
+#include <atomic>
+
+namespace ghip {
+
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+
+static constexpr int G6_BM = 64;                       // rows per workgroup
+static constexpr int G6_LD = QK_K + 16;                // LDS row pitch of the int8 planes
+
+// x f32 [N][K] -> qs int8 [N][K] + d f32 [N][K / 256]; one wave per block, the values of k_quantize_q8_K
+__global__ __launch_bounds__(256) void k_quantize_q8_K_planes(const float *__restrict__ x, int64_t nblocks,
+                                                               uint32_t *__restrict__ qs, float *__restrict__ xd) {
+    const int lane = threadIdx.x & 63;
+    const int64_t blk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (blk >= nblocks) return;                      // wave-uniform
+    const float4 v = reinterpret_cast<const float4 *>(x)[blk * 64 + lane];
+    float d;
+    const uint32_t p = q8k_block_lane(v, lane, d);
+    qs[blk * 64 + lane] = p;
+    if (lane == 0) xd[blk] = d;
+}
+
+hipError_t quantize_q8_K_planes(const float *x, int64_t K, int64_t N, void *qs, float *xd, hipStream_t s) {
+    const int64_t nblocks = N * (K / QK_K);
+    if (nblocks == 0) return hipSuccess;
+    (void)hipGetLastError();  // report only this launch's error
+    launch_k(k_quantize_q8_K_planes, dim3((unsigned)((nblocks + 3) / 4)), dim3(256), 0, s, x, nblocks, (uint32_t *)qs, xd);
+    return hipGetLastError();
+}
+
+// four 6-bit values (one per byte) and their scale -> the int8 digits of w' = sc (q - 32) = 128 hi + lo, packed
+// in element order.  Elements 0, 2 and 1, 3 go through 16-bit pairs: lo = ((w' + 64) & 127) - 64 in [-64, 63],
+// hi = (w' - lo) >> 7 in [-32, 32]; v_perm_b32 interleaves the pairs' low bytes (selector bytes 0..3 name the
+// bytes of the second operand, 4..7 those of the first).
+__device__ __forceinline__ void q6_digits(uint32_t q6, int sc, uint32_t &hi, uint32_t &lo) {
+    const s16x2 s = {(short)sc, (short)sc};
+    const s16x2 c32 = {32, 32}, c64 = {64, 64}, c127 = {127, 127}, c7 = {7, 7};
+    const uint32_t ev_u = q6 & 0x00FF00FFu, od_u = (q6 >> 8) & 0x00FF00FFu;
+    s16x2 ev, od;
+    __builtin_memcpy(&ev, &ev_u, 4);
+    __builtin_memcpy(&od, &od_u, 4);
+    const s16x2 we = (ev - c32) * s, wo = (od - c32) * s;
+    const s16x2 le = ((we + c64) & c127) - c64, lod = ((wo + c64) & c127) - c64;
+    const s16x2 he = (we - le) >> c7, hod = (wo - lod) >> c7;
+    uint32_t le_u, lo_u, he_u, ho_u;
+    __builtin_memcpy(&le_u, &le, 4);
+    __builtin_memcpy(&lo_u, &lod, 4);
+    __builtin_memcpy(&he_u, &he, 4);
+    __builtin_memcpy(&ho_u, &hod, 4);
+    lo = __builtin_amdgcn_perm(lo_u, le_u, 0x06020400u);
+    hi = __builtin_amdgcn_perm(ho_u, he_u, 0x06020400u);
+}
+
+template <int WN, int TN>
+__global__ __launch_bounds__(128 * WN) void k_gemm_q6_K(const uint8_t *__restrict__ W, int nb, int M,
+                                                         const uint8_t *__restrict__ xqs, const float *__restrict__ xd,
+                                                         int N, int ntn, float *__restrict__ y, int64_t ldy) {
+    constexpr int THREADS = 128 * WN;                  // 2 x WN waves
+    constexpr int BN = 32 * WN * TN;                   // columns per workgroup
+    constexpr int RPW = G6_BM / (2 * WN);              // rows a wave decodes per superblock
+    constexpr int XP = BN * 16 / THREADS;              // 16-byte pieces of the x tile per thread (4 TN)
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    uint8_t *whi = smem;                               // [64][G6_LD]
+    uint8_t *wlo = whi + G6_BM * G6_LD;                // [64][G6_LD]
+    uint8_t *xs = wlo + G6_BM * G6_LD;                 // [BN][G6_LD]
+    float *dws = reinterpret_cast<float *>(xs + BN * G6_LD);   // [64]
+    float *dxs = dws + G6_BM;                          // [BN]
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // the column tiles of one row tile are neighbours in the grid (they share the weight rows)
+    const int mt = (int)(blockIdx.x / (unsigned)ntn), nt = (int)(blockIdx.x - (unsigned)mt * (unsigned)ntn);
+    const int m0 = mt * G6_BM, n0 = nt * BN;
+    const int K = nb * QK_K;
+    const int64_t rowbytes = (int64_t)nb * Q6KB;
+
+    // lane t of the decoding wave owns elements 4t .. 4t + 3 of a superblock: group (h, j), one scale
+    const int eh = lane >> 5, ej = (lane >> 3) & 3, ei = lane & 7;
+    const int ql_src = 4 * (16 * eh + 8 * (ej & 1) + ei), ql_sh = 4 * (ej >> 1);   // byte address of the source lane
+    const int qh_src = 4 * (32 + 8 * eh + ei), qh_sh = 2 * ej;
+    const int sc_idx = 8 * eh + 2 * ej + (ei >> 2);
+    const int sc_src = 4 * (48 + (sc_idx >> 2)), sc_sh = 8 * (sc_idx & 3);
+    const int ld_lane = lane < 53 ? lane : 52;
+
+    // (unconditional loads at clamped indices, always inside the operands)
+    const uint8_t *rowp[RPW];
+#pragma unroll
+    for (int u = 0; u < RPW; u++) {
+        const int m = m0 + wave * RPW + u;
+        rowp[u] = W + (int64_t)(m < M ? m : M - 1) * rowbytes;
+    }
+    int xoff[XP];
+#pragma unroll
+    for (int i = 0; i < XP; i++) {
+        const int p = tid + THREADS * i, n = n0 + (p >> 4);
+        xoff[i] = (n < N ? n : N - 1) * K + (p & 15) * 16;             // N K < 2^31 (host check)
+    }
+    const int dn = n0 + (tid & (BN - 1));
+    const int dxoff = (dn < N ? dn : N - 1) * nb;
+
+    struct Regs {                                      // one superblock of the tile's operands, as loaded
+        uint32_t w[RPW];
+        u32x4 x[XP];
+        float dx;
+    };
+    auto prefetch = [&](int b, Regs &g) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < RPW; u++) {
+            // (pointer arithmetic, not an integer round trip: the address stays a global one, no flat load)
+            const uint8_t *p = rowp[u] + b * Q6KB;
+            g.w[u] = reinterpret_cast<const uint32_t *>(p - ((uintptr_t)p & 3))[ld_lane];
+        }
+#pragma unroll
+        for (int i = 0; i < XP; i++) g.x[i] = *reinterpret_cast<const u32x4 *>(xqs + xoff[i] + b * QK_K);
+        g.dx = xd[dxoff + b];
+    };
+    auto stage = [&](int b, const Regs &g) __attribute__((always_inline)) {   // registers of superblock b -> LDS
+        uint32_t dwv = 0;                              // lane u: the fp16 d of the wave's row u
+        // (no branch per row: the rows' cross-lane round trips must overlap)
+#pragma unroll
+        for (int u = 0; u < RPW; u++) {
+            const int r = wave * RPW + u;
+            const uintptr_t a = (uintptr_t)(rowp[u] + b * Q6KB);
+            const uint32_t raw = g.w[u];
+            const uint32_t nx = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)raw, DPP_WAVE_SHL1, 0xF, 0xF, false);
+            const uint32_t own = (a & 2) ? __builtin_amdgcn_alignbyte(nx, raw, 2) : raw;
+            const uint32_t ql = (uint32_t)__builtin_amdgcn_ds_bpermute(ql_src, (int)own) >> ql_sh;
+            const uint32_t qh = (uint32_t)__builtin_amdgcn_ds_bpermute(qh_src, (int)own) >> qh_sh;
+            const int sc = (int)(int8_t)((uint32_t)__builtin_amdgcn_ds_bpermute(sc_src, (int)own) >> sc_sh);
+            const uint32_t dw = (uint32_t)__builtin_amdgcn_readlane((int)own, 52);
+            dwv = lane == u ? dw : dwv;
+            uint32_t hi, lo;
+            q6_digits((ql & 0x0F0F0F0Fu) | ((qh & 0x03030303u) << 4), sc, hi, lo);
+            *reinterpret_cast<uint32_t *>(whi + r * G6_LD + 4 * lane) = hi;
+            *reinterpret_cast<uint32_t *>(wlo + r * G6_LD + 4 * lane) = lo;
+        }
+        if (lane < RPW) dws[wave * RPW + lane] = h2f(dwv);
+#pragma unroll
+        for (int i = 0; i < XP; i++) {
+            const int p = tid + THREADS * i;
+            *reinterpret_cast<u32x4 *>(xs + (p >> 4) * G6_LD + (p & 15) * 16) = g.x[i];
+        }
+        if (tid < BN) dxs[tid] = g.dx;
+    };
+
+    const int wr = wave & 1, wt = wave >> 1;
+    const int c = lane & 31, h = lane >> 5;
+    const uint8_t *bh_p = whi + (32 * wr + c) * G6_LD + 16 * h;
+    const uint8_t *bl_p = wlo + (32 * wr + c) * G6_LD + 16 * h;
+    const uint8_t *a_p = xs + (32 * TN * wt + c) * G6_LD + 16 * h;
+    const i32x16 iz = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    float acc[TN][16];
+#pragma unroll
+    for (int t = 0; t < TN; t++)
+#pragma unroll
+        for (int i = 0; i < 16; i++) acc[t][i] = 0.0f;
+
+    // superblock b: its registers -> LDS, the loads of b + 1 into the same registers, then the MFMAs and the
+    // fp32 step.  (Loading two superblocks ahead measured the same: the stage is bound by instruction issue.)
+    Regs g;
+    prefetch(0, g);
+    for (int b = 0; b < nb; b++) {
+        __syncthreads();                               // the previous superblock's LDS reads are done
+        stage(b, g);
+        __syncthreads();
+        prefetch(b + 1 < nb ? b + 1 : nb - 1, g);
+        i32x16 H[TN], L[TN];
+#pragma unroll
+        for (int t = 0; t < TN; t++) H[t] = L[t] = iz;
+#pragma unroll
+        for (int s = 0; s < QK_K / 32; s++) {
+            const i32x4 bh = *reinterpret_cast<const i32x4 *>(bh_p + 32 * s);
+            const i32x4 bl = *reinterpret_cast<const i32x4 *>(bl_p + 32 * s);
+#pragma unroll
+            for (int t = 0; t < TN; t++) {
+                const i32x4 a = *reinterpret_cast<const i32x4 *>(a_p + 32 * t * G6_LD + 32 * s);
+                H[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bh, H[t], 0, 0, 0);
+                L[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bl, L[t], 0, 0, 0);
+            }
+        }
+        // the superblock's one fp32 step per output: the GEMV's, in the GEMV's order
+        const float dw = dws[32 * wr + c];
+#pragma unroll
+        for (int t = 0; t < TN; t++)
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const int tok = 32 * TN * wt + 32 * t + (i & 3) + 8 * (i >> 2) + 4 * h;
+                const int isum = H[t][i] * 128 + L[t][i];
+                acc[t][i] = __builtin_fmaf(dxs[tok] * dw, (float)isum, acc[t][i]);
+            }
+    }
+
+    const int row = m0 + 32 * wr + c;
+    if (row < M) {
+#pragma unroll
+        for (int t = 0; t < TN; t++)
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const int n = n0 + 32 * TN * wt + 32 * t + (i & 3) + 8 * (i >> 2) + 4 * h;
+                if (n < N) y[(int64_t)n * ldy + row] = acc[t][i];
+            }
+    }
+}
+
+template <int WN, int TN>
+static hipError_t launch_gemm6(const uint8_t *W, int nb, int M, const uint8_t *xqs, const float *xd, int N, float *y,
+                               int64_t ldy, hipStream_t s) {
+    constexpr int BN = 32 * WN * TN;
+    constexpr size_t lds = (size_t)(2 * G6_BM + BN) * G6_LD + (size_t)(G6_BM + BN) * 4;
+    static std::atomic<uint32_t> attr{0};            // one bit per device (16 max), thread-safe
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 15) dev = 0;
+    if (!(attr.load(std::memory_order_acquire) & (1u << dev))) {
+        hipError_t e = hipFuncSetAttribute((const void *)k_gemm_q6_K<WN, TN>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)lds);
+        if (e != hipSuccess) return e;
+        attr.fetch_or(1u << dev, std::memory_order_acq_rel);
+    }
+    const int64_t ntm = ((int64_t)M + G6_BM - 1) / G6_BM, ntn = ((int64_t)N + BN - 1) / BN;
+    if (ntm * ntn >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    (void)hipGetLastError();  // report only this launch's error
+    launch_k(k_gemm_q6_K<WN, TN>, dim3((unsigned)(ntm * ntn)), dim3(128 * WN), lds, s, W, nb, M, xqs, xd, N, (int)ntn, y, ldy);
+    return hipGetLastError();
+}
+
+// y[n * ldy + m] = W[m] . x[n] on the planes quantize_q8_K_planes wrote; any K % 256 == 0, M, N >= 1
+hipError_t gemm_q6_K(const void *W, int64_t K, int64_t M, const void *xqs, const float *xd, int64_t N, float *y,
+                     int64_t ldy, hipStream_t s) {
+    if (K <= 0 || K % QK_K || M < 1 || M >= ((int64_t)1 << 31) || N < 1 || N * K >= ((int64_t)1 << 31))
+        return hipErrorInvalidValue;
+    const int nb = (int)(K / QK_K);
+    const uint8_t *w = (const uint8_t *)W, *q = (const uint8_t *)xqs;
+    if (N <= 64) return launch_gemm6<2, 1>(w, nb, (int)M, q, xd, (int)N, y, ldy, s);
+    if (N <= 128) return launch_gemm6<4, 1>(w, nb, (int)M, q, xd, (int)N, y, ldy, s);
+    return launch_gemm6<4, 2>(w, nb, (int)M, q, xd, (int)N, y, ldy, s);
+}
+
+}  // namespace ghip

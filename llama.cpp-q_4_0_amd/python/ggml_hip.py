@@ -58,6 +58,8 @@ def _bind(L):
         "ggml_hip_quantize_q8_K": ([vp, i64, i64, vp, vp], i32),
         "ggml_hip_dequantize_q6_K": ([vp, i64, i64, vp, vp], i32),
         "ggml_hip_mul_mat_q6_K": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
+        "ggml_hip_debug_q6k_auto_algo": ([i64, i64, i64], i32),
+        "ggml_hip_debug_set_q6k_gemm_min_n": ([i32], i32),
         "ggml_hip_reserve_workspace": ([i64, i64], i32),
         "ggml_hip_reserve_workspace_mm": ([i64, i64, i64], i32),
         "ggml_hip_weight_image_create": ([vp, i64, i64, vp], i32),
@@ -260,7 +262,8 @@ def dequantize_q6_K(wq_dev, K, M, w_dev, stream=None):
 
 
 def mul_mat_q6_K(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_off=0, x_off=0, y_off=0):
-    """Q6_K rows (210 * K / 256 bytes each) x f32 [N][K] -> f32 y[n * ldy + m]; algo 0 auto, 1 GEMV, 4 exact."""
+    """Q6_K rows (210 * K / 256 bytes each) x f32 [N][K] -> f32 y[n * ldy + m]; algo 0 auto (exact mode: 4; N at or
+    above the GEMM threshold, or K > 16384: 5; else 1), 1 GEMV, 4 exact, 5 int8-MFMA GEMM (bitwise algo 1)."""
     check(load().ggml_hip_mul_mat_q6_K(_ptr(w_dev) + w_off, K, M, _ptr(x_dev) + x_off, N, _ptr(y_dev) + y_off,
                                        M if ldy is None else ldy, algo, stream), "mul_mat_q6_K")
 
