@@ -9,7 +9,9 @@
  * Scope: GGML_OP_MUL_MAT with src0 = GGML_TYPE_Q4_0, src1 = dst = GGML_TYPE_F32
  * (the path BASELINE.json names), and the same with src0 = GGML_TYPE_Q6_K: the
  * output.weight a k-quants build's quantizer writes into every q4_0 file
- * (llama.cpp:2416-2421; ggml_vec_dot_q6_K_q8_K semantics, k_quants.c).  Everything
+ * (llama.cpp:2416-2421; ggml_vec_dot_q6_K_q8_K semantics, k_quants.c), and with
+ * src0 = GGML_TYPE_Q8_0: the matrices of a "mostly Q8_0" file
+ * (ggml_vec_dot_q8_0_q8_0 semantics).  Everything
  * else, the other k-quant types included, returns "cannot" so ggml's
  * CPU path runs, exactly as ggml_cuda_can_mul_mat / ggml_cuda_compute_forward
  * return false for what they do not handle.
@@ -173,6 +175,25 @@ int ggml_hip_debug_q6k_auto_algo(int64_t K, int64_t M, int64_t N);
 /* debug: the smallest N at which auto takes the GEMM (default: the measured crossover; GGML_HIP_Q6K_GEMM_MIN_N;
  * values below 9 count as 9); -1 restores the environment value or the default.  Returns the previous value. */
 int ggml_hip_debug_set_q6k_gemm_min_n(int n);
+/* Q8_0 WEIGHTS (block_q8_0 rows, 34 bytes per 32 weights; dev_w 4-byte aligned, K % 64 == 0 so every row is) x F32
+ * -> F32 with the semantics of ggml_vec_dot_q8_0_q8_0 on the bit-exact q8_0 of x.  Stream-ordered and
+ * graph-capturable once ggml_hip_reserve_workspace_mm(K, N, M) has run (it covers the prefill path's per-call
+ * weight image, 34 bytes per 32 weights, and the exact mode's q8_0 of x).  Status codes as for the q4_0 entry
+ * points; K % 64 != 0 or ldy < M -> GGML_HIP_ERR_INVALID; N = 0 -> GGML_HIP_OK.
+ * dequantize_q8_0: dequantize_row_q8_0 (ggml.c:1594-1610), bit-exact. */
+int ggml_hip_dequantize_q8_0(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream);
+/* y[n*ldy + m] = W[m] . x[n].  algo: 0 auto (4 in exact mode; else 1 below the GEMM threshold; else 2), 1 GEMV
+ * with the q8_0 quantization of x fused in (column tiles of 8 for N > 8, fewer above K = 7232; a column's y is
+ * bitwise the same in every tile and under every launch policy), 2 the weight's int8 image built per call into the
+ * workspace, then the int8-MFMA GEMM of the q4_0 path (k_gemm8) unchanged, 4 exact: bit-identical to the AVX2
+ * branch of ggml_vec_dot_q8_0_q8_0 (ggml.c:3231-3320).  Anything else -> GGML_HIP_ERR_INVALID. */
+int ggml_hip_mul_mat_q8_0(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N,
+                          float *dev_y, int64_t ldy, int algo, void *stream);
+/* debug, no device needed: the algo that algo 0 of ggml_hip_mul_mat_q8_0 would run now: 1, 2 or 4 */
+int ggml_hip_debug_q8_0_auto_algo(int64_t K, int64_t M, int64_t N);
+/* debug: the smallest N at which auto takes the GEMM (default 32: the measured crossover; GGML_HIP_Q8_0_GEMM_MIN_N; values
+ * below 9 count as 9); -1 restores the environment value or the default.  Returns the previous value. */
+int ggml_hip_debug_set_q8_0_gemm_min_n(int n);
 
 /* Sibling mul_mats that share the activation x (ggml graphs issue wq/wk/wv and w1/w3 on the same
  * src1): n <= 4 weight matrices of the same K, y_i = W_i x with y_i f32 [N][M_i].  One launch for

@@ -70,6 +70,33 @@ int ggml_hip_debug_q6k_auto_algo(int64_t K, int64_t M, int64_t N) {
 
 int ggml_hip_debug_set_q6k_gemm_min_n(int n) { return q6k_set_gemm_min_n(n); }
 
+int ggml_hip_dequantize_q8_0(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
+    if (!dev_w || !dev_wq || K <= 0 || K % QK || M < 0) return fail(GGML_HIP_ERR_INVALID, "bad arguments");
+    if (!aligned(dev_wq, 2) || !aligned(dev_w, 16))
+        return fail(GGML_HIP_ERR_INVALID, "w must be 16-byte aligned, the Q8_0 rows 2-byte aligned");
+    HIP_RET(ghip::dequantize_q8_0(dev_wq, K, M, dev_w, resolve_stream(stream)));
+    return GGML_HIP_OK;
+}
+
+int ggml_hip_mul_mat_q8_0(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N, float *dev_y,
+                          int64_t ldy, int algo, void *stream) {
+    ensure_init();
+    return mul_mat_q8_0_dev(dev_w, K, M, dev_x, N, dev_y, ldy, algo, resolve_stream(stream));
+}
+
+int ggml_hip_debug_q8_0_auto_algo(int64_t K, int64_t M, int64_t N) {
+    if (K <= 0 || K % 64 || M <= 0 || N < 0) return fail(GGML_HIP_ERR_INVALID, "bad shape");
+    return q8_0_auto_algo(K, M, N);
+}
+
+int ggml_hip_debug_set_q8_0_gemm_min_n(int n) { return q8_0_set_gemm_min_n(n); }
+
+/* not in the public header: force the Q8_0 GEMV's launch policy (tests: every policy gives the same y bitwise) */
+int ggml_hip_debug_set_q8_0_gemv_policy(int map, int depth, int wg_per_cu) {
+    ghip::gemv_q8_0w_set_policy(map, depth, wg_per_cu);
+    return GGML_HIP_OK;
+}
+
 int ggml_hip_mul_mat_q4_0_multi(int n, const void *const *dev_w, const int64_t *M, int64_t K, const float *dev_x,
                                 int64_t N, float *const *dev_y, void *stream) {
     ensure_init();

@@ -367,6 +367,76 @@ int mul_mat_q6k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t
     return GGML_HIP_OK;
 }
 
+// The Q8_0-weight mul_mat (q8_0_w.hip).  Decode: the fused GEMV (column tiles above gemv_q8_0w_max_tokens(K)).
+// Prefill: the weight's k_gemm8 image built per call into the stream's workspace (k_prep8_w_q8_0; the way GEMM
+// version 9 treats an unregistered q4_0 weight; ggml_hip_reserve_workspace_mm budgets its 34 B per 32 weights),
+// then gemm8_prep_x + gemm8_run unchanged.  Exact mode: the SoA q8_0 quantizer into the workspace and the exact
+// kernel.  Auto takes the GEMM from N >= q8_0_gemm_min_n() (tools/q8_0_bench.py, DESIGN §4b;
+// GGML_HIP_Q8_0_GEMM_MIN_N / ggml_hip_debug_set_q8_0_gemm_min_n, never below 9) and wherever the GEMV cannot
+// run (one token's q8_0 larger than the LDS).
+// the sweep (profiles/q8_0_gemm.json, 4096 x 4096): the tiled GEMV wins at N = 9 and 16 (16.2 / 22.7 us against
+// the GEMM arm's flat 35 us, most of it the per-call image), the GEMM from N = 32 (35.3 against 43.4 us)
+static constexpr int Q8_0_GEMM_MIN_N = 32;
+std::atomic<int> g_q8_0_min_n{-1};
+int q8_0_gemm_min_n() {
+    int v = g_q8_0_min_n.load(std::memory_order_relaxed);
+    if (v < 0) {
+        const char *e = getenv("GGML_HIP_Q8_0_GEMM_MIN_N");
+        int want = e ? atoi(e) : Q8_0_GEMM_MIN_N, expect = -1;
+        if (want < 9) want = 9;
+        g_q8_0_min_n.compare_exchange_strong(expect, want);
+        v = g_q8_0_min_n.load(std::memory_order_relaxed);
+    }
+    return v;
+}
+int q8_0_set_gemm_min_n(int n) {
+    const int prev = q8_0_gemm_min_n();
+    g_q8_0_min_n.store(n < 0 ? -1 : (n < 9 ? 9 : n), std::memory_order_relaxed);    // -1: re-read the environment
+    return prev;
+}
+int q8_0_auto_algo(int64_t K, int64_t, int64_t N) {
+    if (exact_mode()) return 4;
+    return (N >= q8_0_gemm_min_n() || ghip::gemv_q8_0w_max_tokens(K) < 1) ? 2 : 1;
+}
+
+int mul_mat_q8_0_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                     hipStream_t s) {
+    if (!w || !x || !y || K <= 0 || M <= 0 || N < 0) return fail(GGML_HIP_ERR_INVALID, "null pointer or bad shape");
+    if (K % 64 != 0) return fail(GGML_HIP_ERR_INVALID, "K must be a multiple of 64 (ggml.c:3236 nb % 2 == 0)");
+    if (N == 0) return GGML_HIP_OK;
+    if (ldy < M) return fail(GGML_HIP_ERR_INVALID, "ldy < M");
+    if (!aligned(w, 4) || !aligned(x, 16) || !aligned(y, 4))
+        return fail(GGML_HIP_ERR_INVALID, "W must be 4-byte, x 16-byte, y 4-byte aligned");
+    if (M >= (1 << 30) || N * K >= ((int64_t)1 << 31))
+        return fail(GGML_HIP_ERR_UNSUPPORTED, "matrix too large for 32-bit indices; split rows or columns");
+    const int id = current_device();
+    if (algo == 0) algo = q8_0_auto_algo(K, M, N);
+    if (algo == 1) {
+        if (ghip::gemv_q8_0w_max_tokens(K) < 1) return fail(GGML_HIP_ERR_UNSUPPORTED, "K too long for the Q8_0 GEMV");
+        HIP_RET(ghip::gemv_q8_0w(w, K, M, x, N, y, ldy, g_dev[id].info, s));
+        return GGML_HIP_OK;
+    }
+    if (algo != 2 && algo != 4) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1, 2 or 4");
+    void *ws = nullptr;
+    if (algo == 2) {
+        if ((N + 7) / 8 > 65535) return fail(GGML_HIP_ERR_UNSUPPORTED, "too many columns for one launch; split columns");
+        const int wrc = stream_workspace(id, s, workspace_bytes_mm(K, N, M), &ws);
+        if (wrc != GGML_HIP_OK) return wrc;
+        void *xws = (char *)ws + ws_g8x_offset(K, N), *wws = (char *)ws + ws_g8w_offset(K, N);
+        HIP_RET(ghip::gemm8_prep_x(x, K, N, xws, s));
+        HIP_RET(ghip::gemm8_prep_w_q8_0(w, K, M, wws, s));
+        HIP_RET(ghip::gemm8_run(wws, K, M, xws, N, y, ldy, s));
+        return GGML_HIP_OK;
+    }
+    const int wrc = stream_workspace(id, s, workspace_bytes(K, N), &ws);
+    if (wrc != GGML_HIP_OK) return wrc;
+    int8_t *qs = (int8_t *)ws;
+    float *xd = (float *)((char *)ws + ((size_t)(N * K + 255) & ~(size_t)255));
+    HIP_RET(ghip::quantize_q8_0_soa(x, K, N, qs, xd, s));
+    HIP_RET(ghip::mm_exact_q8_0w(w, K, M, qs, xd, N, y, ldy, s));
+    return GGML_HIP_OK;
+}
+
 // Sibling matrices (one x) that all take k_gemm9 on a registered fp6 image: ONE launch over their
 // row tiles (the x image built once, as before).  The launch plans its tiles (128 x 128 / 128 x 64 /
 // mixed, half tiles) from its own total tile count, which can differ from the per-matrix launches'
@@ -438,6 +508,15 @@ bool supported_mul_mat(const tensor *src0, const tensor *src1, const tensor *dst
 bool supported_mul_mat_q6k(const tensor *src0, const tensor *src1, const tensor *dst) {
     return src0 && src1 && dst && src0->type == gabi::TYPE_Q6_K && src1->type == gabi::TYPE_F32 &&
            dst->type == gabi::TYPE_F32 && src0->ne[0] > 0 && src0->ne[0] % QK_K == 0 && src0->ne[0] == src1->ne[0] &&
+           dst->ne[0] == src0->ne[1] && dst->ne[1] == src1->ne[1] && src0->ne[2] == src1->ne[2] &&
+           src0->ne[3] == src1->ne[3] && is_contiguous(src0) && is_contiguous(src1) && is_contiguous(dst);
+}
+
+// contiguous Q8_0 x F32 -> F32 (the layer matrices of a "mostly Q8_0" file); a predicate of its own for the same
+// reason: no Q8_0 node reaches a q4_0 or Q6_K kernel, a weight image, a sibling group or a chain
+bool supported_mul_mat_q8_0(const tensor *src0, const tensor *src1, const tensor *dst) {
+    return src0 && src1 && dst && src0->type == gabi::TYPE_Q8_0 && src1->type == gabi::TYPE_F32 &&
+           dst->type == gabi::TYPE_F32 && src0->ne[0] > 0 && src0->ne[0] % 64 == 0 && src0->ne[0] == src1->ne[0] &&
            dst->ne[0] == src0->ne[1] && dst->ne[1] == src1->ne[1] && src0->ne[2] == src1->ne[2] &&
            src0->ne[3] == src1->ne[3] && is_contiguous(src0) && is_contiguous(src1) && is_contiguous(dst);
 }

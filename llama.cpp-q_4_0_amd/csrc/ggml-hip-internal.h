@@ -164,6 +164,13 @@ int q6k_gemm_min_n();
 int q6k_set_gemm_min_n(int n);                          // -1: the environment value or the default; returns the previous
 int mul_mat_q6k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
                     hipStream_t s);
+// the Q8_0-weight mul_mat: algo 0 auto (q8_0_auto_algo), 1 GEMV (column tiles), 2 per-call int8 image + k_gemm8,
+// 4 exact
+int q8_0_auto_algo(int64_t K, int64_t M, int64_t N);    // what algo 0 runs now: 1, 2 or 4 (no device needed)
+int q8_0_gemm_min_n();
+int q8_0_set_gemm_min_n(int n);                         // -1: the environment value or the default; returns the previous
+int mul_mat_q8_0_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                     hipStream_t s);
 // true when ggml_hip_mul_mat_q4_0_multi runs these n siblings at N tokens as ONE k_gemm9 launch on registered
 // fp6 images (mul_mat_group_g9 for n > 1, mul_mat_dev's image GEMM for n = 1); img[i] = the images
 bool g9_images(int n, const void *const *w, const int64_t *M, int64_t K, int64_t N, const void **img);
@@ -174,6 +181,7 @@ bool on_device(const tensor *t);
 void split_range(int64_t nrows, int id, int64_t *lo, int64_t *hi);
 bool supported_mul_mat(const tensor *src0, const tensor *src1, const tensor *dst);
 bool supported_mul_mat_q6k(const tensor *src0, const tensor *src1, const tensor *dst);
+bool supported_mul_mat_q8_0(const tensor *src0, const tensor *src1, const tensor *dst);
 [[noreturn]] void op_abort(const tensor *t, const char *why);
 inline bool same_shape(const tensor *a, const tensor *b) {
     return a->ne[0] == b->ne[0] && a->ne[1] == b->ne[1] && a->ne[2] == b->ne[2] && a->ne[3] == b->ne[3];

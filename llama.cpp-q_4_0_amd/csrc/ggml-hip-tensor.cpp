@@ -114,20 +114,24 @@ void ggml_hip_set_tensor_split(const float *tensor_split) {
 }
 
 bool ggml_hip_can_mul_mat(const struct ggml_tensor *src0_, const struct ggml_tensor *src1_, struct ggml_tensor *dst_) {
-    // ggml-cuda.cu:2595-2610, restricted to the q4_0 path this backend implements and the Q6_K output.weight
+    // ggml-cuda.cu:2595-2610, restricted to the q4_0 path this backend implements, the Q6_K output.weight and
+    // Q8_0 weights
     const tensor *src0 = (const tensor *)src0_, *src1 = (const tensor *)src1_, *dst = (const tensor *)dst_;
-    if (!supported_mul_mat(src0, src1, dst) && !supported_mul_mat_q6k(src0, src1, dst)) return false;
+    if (!supported_mul_mat(src0, src1, dst) && !supported_mul_mat_q6k(src0, src1, dst) &&
+        !supported_mul_mat_q8_0(src0, src1, dst))
+        return false;
     // no device: decline, so ggml.c plans and runs its own CPU mul_mat (the reference would route
     // the op here regardless and fail inside ggml_cuda_mul_mat)
     ensure_init();
     if (g_device_count == 0) return false;
     if (dst->ne[0] >= 32 && dst->ne[1] >= 32 && src1->ne[0] >= 32) return true;
-    // Decode (N < 32) of a host-resident Q4_0 (or Q6_K) weight: the reference declines it (each call would
+    // Decode (N < 32) of a host-resident Q4_0 (or Q6_K, Q8_0) weight: the reference declines it (each call would
     // re-upload the weight, ggml-cuda.cu:2496-2502), so the arch/ frontends, which never offload,
     // decode on the CPU.  Here the weight-residency cache keeps the weight on the device after its
     // first use, so a weight of at least GGML_HIP_DECODE_MIN_WEIGHTS elements (default 2^19: one
     // LLaMA/Falcon projection is 2^24) is taken at any N; smaller ones stay on ggml's CPU op.
-    return (src0->type == gabi::TYPE_Q4_0 || src0->type == gabi::TYPE_Q6_K) && wcache_enabled() &&
+    return (src0->type == gabi::TYPE_Q4_0 || src0->type == gabi::TYPE_Q6_K || src0->type == gabi::TYPE_Q8_0) &&
+           wcache_enabled() &&
            (uint64_t)src0->ne[0] * (uint64_t)src0->ne[1] >= (uint64_t)decode_min_weights();
 }
 
@@ -145,14 +149,18 @@ void ggml_hip_mul_mat(const struct ggml_tensor *src0, const struct ggml_tensor *
 
 namespace ghh {
 
-// the q4_0 (or Q6_K) mul_mat of one node; leaves a pending fusion chain alone (try_fuse checked that the two
+// the q4_0 (or Q6_K, Q8_0) mul_mat of one node; leaves a pending fusion chain alone (try_fuse checked that the two
 // touch disjoint buffers)
 void mul_mat_node(const tensor *src0, const tensor *src1, tensor *dst) {
     // ggml_cuda_mul_mat -> ggml_cuda_op (ggml-cuda.cu:2671-2690, 2286-2567)
-    const bool q6 = supported_mul_mat_q6k(src0, src1, dst);    // dispatch by type: never a q4_0 kernel or image
-    if (!q6 && !supported_mul_mat(src0, src1, dst)) {
-        fprintf(stderr, "ggml_hip_mul_mat: unsupported operands (need contiguous Q4_0 x F32 -> F32, K %% 64 == 0, or "
-                        "Q6_K x F32 -> F32, K %% 256 == 0)\n");
+    // dispatch by weight type: a Q6_K or Q8_0 node never reaches a q4_0 kernel or image, nor one another's
+    const gabi::type wtype = supported_mul_mat(src0, src1, dst)        ? gabi::TYPE_Q4_0
+                             : supported_mul_mat_q6k(src0, src1, dst)  ? gabi::TYPE_Q6_K
+                             : supported_mul_mat_q8_0(src0, src1, dst) ? gabi::TYPE_Q8_0
+                                                                       : gabi::TYPE_COUNT;
+    if (wtype == gabi::TYPE_COUNT) {
+        fprintf(stderr, "ggml_hip_mul_mat: unsupported operands (need contiguous Q4_0 or Q8_0 x F32 -> F32, K %% 64 == 0, "
+                        "or Q6_K x F32 -> F32, K %% 256 == 0)\n");
         abort();
     }
     const int64_t K = src0->ne[0], M = src0->ne[1], N = src1->ne[1];
@@ -173,7 +181,7 @@ void mul_mat_node(const tensor *src0, const tensor *src1, tensor *dst) {
     const bool src0_dev = on_device(src0);
     const bool src1_dev = src1->backend == gabi::BACKEND_GPU;
     const bool dst_dev = dst->backend == gabi::BACKEND_GPU;
-    const size_t wrow = src0->nb[1];                   // 18 K / 32 (Q4_0) or 210 K / 256 (Q6_K)
+    const size_t wrow = src0->nb[1];                   // 18 K / 32 (Q4_0), 210 K / 256 (Q6_K) or 34 K / 32 (Q8_0)
     const int saved = current_device();
     const int main_id = g_main_device;
     const uint64_t call_id = wcache_next_call_id();
@@ -226,8 +234,8 @@ void mul_mat_node(const tensor *src0, const tensor *src1, tensor *dst) {
             }
             // prefill (N > IMG_MIN_N) of a resident weight: build its image once (fp6 for k_gemm9, int8
             // under version 8; a failure to allocate it leaves the q4_0 bytes to k_gemm7 / split-K)
-            if (!q6 && w_resident && N > IMG_MIN_N && !exact_mode() && (gemm_version() == 8 || gemm_version() == 10) &&
-                (src0_dev || wcache_images_enabled())) {
+            if (wtype == gabi::TYPE_Q4_0 && w_resident && N > IMG_MIN_N && !exact_mode() &&
+                (gemm_version() == 8 || gemm_version() == 10) && (src0_dev || wcache_images_enabled())) {
                 const bool had = wimage_find(id, w, K, rows) != nullptr;
                 if (wimage_ensure(id, w, K, rows, s) && !had && !src0_dev)
                     wcache_note_image(id, w, image_format() == 9 ? ghip::gemm9_w_bytes(K, rows) : ghip::gemm8_w_bytes(K, rows),
@@ -262,8 +270,13 @@ void mul_mat_node(const tensor *src0, const tensor *src1, tensor *dst) {
                 y = (float *)tmp_alloc(id, (size_t)N * rows * 4);
                 ldy = rows;
             }
-            if ((q6 ? mul_mat_q6k_dev(w, K, rows, x, N, y, ldy, 0, s) : mul_mat_dev(w, K, rows, x, N, y, ldy, 0, s)) !=
-                GGML_HIP_OK) {
+            int rc;
+            switch (wtype) {
+                case gabi::TYPE_Q6_K: rc = mul_mat_q6k_dev(w, K, rows, x, N, y, ldy, 0, s); break;
+                case gabi::TYPE_Q8_0: rc = mul_mat_q8_0_dev(w, K, rows, x, N, y, ldy, 0, s); break;
+                default: rc = mul_mat_dev(w, K, rows, x, N, y, ldy, 0, s); break;
+            }
+            if (rc != GGML_HIP_OK) {
                 fprintf(stderr, "ggml_hip_mul_mat: %s\n", g_last_error.c_str());
                 abort();
             }
@@ -343,8 +356,8 @@ void ggml_hip_transform_tensor(void *data, struct ggml_tensor *tensor_) {
     ensure_init();
     flush_deferred();
     tensor *t = (tensor *)tensor_;
-    if ((t->type != gabi::TYPE_Q4_0 && t->type != gabi::TYPE_Q6_K && t->type != gabi::TYPE_F32 &&
-         t->type != gabi::TYPE_F16) || g_device_count == 0) {
+    if ((t->type != gabi::TYPE_Q4_0 && t->type != gabi::TYPE_Q6_K && t->type != gabi::TYPE_Q8_0 &&
+         t->type != gabi::TYPE_F32 && t->type != gabi::TYPE_F16) || g_device_count == 0) {
         // A type no device op reads: ggml.c computes the ops that read it on the CPU and asserts
         // CPU operands there (ggml.c:15650), so the tensor stays a CPU tensor, on a host copy this
         // backend owns (the loader may free `data` after the call, llama.cpp:680-683).
@@ -364,8 +377,9 @@ void ggml_hip_transform_tensor(void *data, struct ggml_tensor *tensor_) {
         t->extra = nullptr;
         return;
     }
-    if (t->type != gabi::TYPE_Q4_0 && t->type != gabi::TYPE_Q6_K && t->backend == gabi::BACKEND_GPU_SPLIT)
-        t->backend = gabi::BACKEND_GPU;   // only the Q4_0 / Q6_K mul_mats read row-split operands
+    if (t->type != gabi::TYPE_Q4_0 && t->type != gabi::TYPE_Q6_K && t->type != gabi::TYPE_Q8_0 &&
+        t->backend == gabi::BACKEND_GPU_SPLIT)
+        t->backend = gabi::BACKEND_GPU;   // only the Q4_0 / Q6_K / Q8_0 mul_mats read row-split operands
     const int64_t nrows = gabi::nrows(t);
     const size_t nb1 = t->nb[1];
     auto *extra = new ggml_tensor_extra_gpu;
@@ -485,8 +499,9 @@ void ggml_hip_free_scratch(void) {
 bool ggml_hip_compute_forward(struct ggml_compute_params *params_, struct ggml_tensor *tensor_) {
     // ggml-cuda.cu:2933-3021: a node is taken when any operand is device resident (MUL_MAT also when
     // can_mul_mat holds for host operands); only ith == 0 in COMPUTE executes (the other threads
-    // spin in ggml.c:17285-17287).  Q4_0 mul_mat -> the q4_0 kernels, Q6_K mul_mat -> q6_k.hip; F16 mul_mat
-    // (attention on the KV cache) and the other ops of a LLaMA layer -> ggml_ops.hip; views are free.
+    // spin in ggml.c:17285-17287).  Q4_0 mul_mat -> the q4_0 kernels, Q6_K mul_mat -> q6_k.hip, Q8_0 mul_mat ->
+    // q8_0_w.hip; F16 mul_mat (attention on the KV cache) and the other ops of a LLaMA layer -> ggml_ops.hip; views
+    // are free.
     const gabi::compute_params *params = (const gabi::compute_params *)params_;
     tensor *t = (tensor *)tensor_;
     // a host write into cached weights (LoRA apply) invalidates their device copies; INIT runs once per
@@ -504,7 +519,9 @@ bool ggml_hip_compute_forward(struct ggml_compute_params *params_, struct ggml_t
                 f16_mul_mat = true;
                 break;
             }
-            if (!supported_mul_mat(t->src0, t->src1, t) && !supported_mul_mat_q6k(t->src0, t->src1, t)) return false;
+            if (!supported_mul_mat(t->src0, t->src1, t) && !supported_mul_mat_q6k(t->src0, t->src1, t) &&
+                !supported_mul_mat_q8_0(t->src0, t->src1, t))
+                return false;
             ensure_init();
             if (g_device_count == 0) return false;
             if (!any_on_device && !ggml_hip_can_mul_mat((const ggml_tensor *)t->src0, (const ggml_tensor *)t->src1,

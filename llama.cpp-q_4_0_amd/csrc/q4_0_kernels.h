@@ -153,6 +153,22 @@ hipError_t quantize_q8_K_planes(const float *x, int64_t K, int64_t N, void *qs, 
 hipError_t gemm_q6_K(const void *W, int64_t K, int64_t M, const void *xqs, const float *xd, int64_t N, float *y,
                      int64_t ldy, hipStream_t s);
 
+// Q8_0 weights (q8_0_w.hip): the layer matrices of a "mostly Q8_0" file.  W: ggml block_q8_0 rows, verbatim
+// (34 bytes per 32 weights, rows 4-byte aligned: K % 64 == 0).
+hipError_t dequantize_q8_0(const void *wq, int64_t K, int64_t M, float *w, hipStream_t s);
+// fused q8_0 quantize of x (LDS) + q8_0.q8_0 GEMV; N > gemv_q8_0w_max_tokens(K) runs column tiles (a column's y
+// does not depend on its tile); max_tokens is 8 up to K = 7232 and 0 where one token's q8_0 exceeds the LDS
+int gemv_q8_0w_max_tokens(int64_t K);
+hipError_t gemv_q8_0w(const void *W, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
+                      const DeviceInfo &dev, hipStream_t s);
+// test hook: force the launch policy (row mapping -1 auto / 0 / 1 / 2, ring depth 0 auto / 1 / 2, workgroups per CU)
+void gemv_q8_0w_set_policy(int map, int depth, int wg_per_cu);
+// exact mode: y bit-identical to the AVX2 ggml_vec_dot_q8_0_q8_0 on the SoA q8_0 of x (quantize_q8_0_soa); any N
+hipError_t mm_exact_q8_0w(const void *W, int64_t K, int64_t M, const int8_t *xqs, const float *xd, int64_t N, float *y,
+                          int64_t ldy, hipStream_t s);
+// prefill: the k_gemm8 weight image (gemm8_w_bytes(K, M) bytes) from Q8_0 rows; then gemm8_prep_x + gemm8_run
+hipError_t gemm8_prep_w_q8_0(const void *W, int64_t K, int64_t M, void *wws, hipStream_t s);
+
 // Multi-GPU helper: y[n*ldy + row0[r] + i] = slab[r][n][i] for i < rows[r] (gather compaction).
 // row_begin travels as a kernel argument (no host->device copy, capture-safe)
 static constexpr int SCATTER_MAX_RANKS = 256;

@@ -60,6 +60,10 @@ def _bind(L):
         "ggml_hip_mul_mat_q6_K": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
         "ggml_hip_debug_q6k_auto_algo": ([i64, i64, i64], i32),
         "ggml_hip_debug_set_q6k_gemm_min_n": ([i32], i32),
+        "ggml_hip_dequantize_q8_0": ([vp, i64, i64, vp, vp], i32),
+        "ggml_hip_mul_mat_q8_0": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
+        "ggml_hip_debug_q8_0_auto_algo": ([i64, i64, i64], i32),
+        "ggml_hip_debug_set_q8_0_gemm_min_n": ([i32], i32),
         "ggml_hip_reserve_workspace": ([i64, i64], i32),
         "ggml_hip_reserve_workspace_mm": ([i64, i64, i64], i32),
         "ggml_hip_weight_image_create": ([vp, i64, i64, vp], i32),
@@ -268,6 +272,17 @@ def mul_mat_q6_K(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_
                                        M if ldy is None else ldy, algo, stream), "mul_mat_q6_K")
 
 
+def dequantize_q8_0(wq_dev, K, M, w_dev, stream=None):
+    check(load().ggml_hip_dequantize_q8_0(_ptr(wq_dev), K, M, _ptr(w_dev), stream), "dequantize_q8_0")
+
+
+def mul_mat_q8_0(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_off=0, x_off=0, y_off=0):
+    """Q8_0 weight rows (34 * K / 32 bytes each) x f32 [N][K] -> f32 y[n * ldy + m]; algo 0 auto (exact mode: 4; N
+    below the GEMM threshold: 1; else 2), 1 GEMV, 2 per-call int8 image + int8-MFMA GEMM, 4 exact."""
+    check(load().ggml_hip_mul_mat_q8_0(_ptr(w_dev) + w_off, K, M, _ptr(x_dev) + x_off, N, _ptr(y_dev) + y_off,
+                                       M if ldy is None else ldy, algo, stream), "mul_mat_q8_0")
+
+
 class ChainTask(ctypes.Structure):
     """struct ggml_hip_chain_task (include/ggml-hip.h)"""
     _fields_ = [("nmat", ctypes.c_int), ("K", ctypes.c_int64), ("x", ctypes.c_void_p),
@@ -380,6 +395,7 @@ class Graph:
 
 GGML_TYPE_F32, GGML_TYPE_Q4_0 = 0, 2
 GGML_TYPE_Q6_K = 14
+GGML_TYPE_Q8_0 = 8
 GGML_BACKEND_CPU, GGML_BACKEND_GPU, GGML_BACKEND_GPU_SPLIT = 0, 10, 20
 GGML_OP_MUL_MAT = 32
 GGML_TASK_INIT, GGML_TASK_COMPUTE, GGML_TASK_FINALIZE = 0, 1, 2
@@ -420,6 +436,9 @@ def make_tensor(gtype, ne, data=None, backend=GGML_BACKEND_CPU):
     elif gtype == GGML_TYPE_Q6_K:
         t.nb[0] = 210
         t.nb[1] = 210 * ne[0] // 256
+    elif gtype == GGML_TYPE_Q8_0:
+        t.nb[0] = 34
+        t.nb[1] = 34 * ne[0] // 32
     else:
         t.nb[0] = 4
         t.nb[1] = 4 * ne[0]
