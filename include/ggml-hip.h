@@ -11,8 +11,12 @@
  * output.weight a k-quants build's quantizer writes into every q4_0 file
  * (llama.cpp:2416-2421; ggml_vec_dot_q6_K_q8_K semantics, k_quants.c), and with
  * src0 = GGML_TYPE_Q8_0: the matrices of a "mostly Q8_0" file
- * (ggml_vec_dot_q8_0_q8_0 semantics).  Everything
- * else, the other k-quant types included, returns "cannot" so ggml's
+ * (ggml_vec_dot_q8_0_q8_0 semantics), and with src0 = GGML_TYPE_Q5_K: the layer
+ * matrices of a "mostly Q5_K" file (ggml_vec_dot_q5_K_q8_K semantics).
+ * src0 = GGML_TYPE_Q4_K (a "mostly Q4_K" file) is taken on this hook path only
+ * with GGML_HIP_Q4_K=1 / ggml_hip_debug_set_q4_K(1) (off by default);
+ * the tensor-free ggml_hip_mul_mat_q4_K always runs.  Everything
+ * else (Q2_K, Q3_K, Q4_1, Q5_0, Q5_1; Q4_K with its switch off) returns "cannot" so ggml's
  * CPU path runs, exactly as ggml_cuda_can_mul_mat / ggml_cuda_compute_forward
  * return false for what they do not handle.
  *
@@ -194,6 +198,28 @@ int ggml_hip_debug_q8_0_auto_algo(int64_t K, int64_t M, int64_t N);
 /* debug: the smallest N at which auto takes the GEMM (default 32: the measured crossover; GGML_HIP_Q8_0_GEMM_MIN_N; values
  * below 9 count as 9); -1 restores the environment value or the default.  Returns the previous value. */
 int ggml_hip_debug_set_q8_0_gemm_min_n(int n);
+/* Q5_K / Q4_K WEIGHTS (block_q5_K rows, 176 bytes per 256 weights; block_q4_K rows, 144 bytes; dev_w 16-byte
+ * aligned, so every block and row is) x F32 -> F32 with the semantics of ggml_vec_dot_q5_K_q8_K /
+ * ggml_vec_dot_q4_K_q8_K on the bit-exact q8_K of x.  K % 256 == 0.  Stream-ordered and capturable (exact mode
+ * after ggml_hip_reserve_workspace).  No byte outside the matrix is read.  Status codes as for the q4_0 entry
+ * points; N == 0 is a no-op.
+ * dequantize_q5_K / _q4_K: dequantize_row_q5_K (k_quants.c:926-969) / dequantize_row_q4_K (733-770), bit-exact. */
+int ggml_hip_dequantize_q5_K(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream);
+int ggml_hip_dequantize_q4_K(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream);
+/* y[n * ldy + m], ldy >= M.  algo: 0 auto (4 in exact mode and for K > 16384, else 1), 1 GEMV (K <= 16384) with the q8_K
+ * quantization of x fused in, exact int32 superblock sums and one fixed fp32 order per superblock (column tiles of
+ * 8 for N > 8, bitwise the per-tile calls; y does not depend on the launch geometry), 4 exact: bit-identical to the
+ * AVX2 branch of ggml_vec_dot_q5_K_q8_K (k_quants.c:2927-3010) / ggml_vec_dot_q4_K_q8_K (2450-2513).  Anything
+ * else -> GGML_HIP_ERR_INVALID. */
+int ggml_hip_mul_mat_q5_K(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N,
+                          float *dev_y, int64_t ldy, int algo, void *stream);
+int ggml_hip_mul_mat_q4_K(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N,
+                          float *dev_y, int64_t ldy, int algo, void *stream);
+/* the hook path (can_mul_mat, transform_tensor, compute_forward, ggml_hip_mul_mat) takes GGML_TYPE_Q4_K tensors
+ * only while this switch is on; off by default (or GGML_HIP_Q4_K=1 in the environment).  Returns the previous
+ * value (0 / 1).  Tensors uploaded while it was on stay on the device, keep being served by
+ * compute_forward after it is turned off (their data is not on the host), and are freed by ggml_hip_free_data. */
+int ggml_hip_debug_set_q4_K(int on);
 
 /* Sibling mul_mats that share the activation x (ggml graphs issue wq/wk/wv and w1/w3 on the same
  * src1): n <= 4 weight matrices of the same K, y_i = W_i x with y_i f32 [N][M_i].  One launch for

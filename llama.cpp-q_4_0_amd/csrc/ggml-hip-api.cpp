@@ -91,6 +91,37 @@ int ggml_hip_debug_q8_0_auto_algo(int64_t K, int64_t M, int64_t N) {
 
 int ggml_hip_debug_set_q8_0_gemm_min_n(int n) { return q8_0_set_gemm_min_n(n); }
 
+static int dequantize_q45k(bool qh, const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
+    if (!dev_w || !dev_wq || K <= 0 || K % QK_K || M < 0) return fail(GGML_HIP_ERR_INVALID, "bad arguments");
+    if (!aligned(dev_wq, 16) || !aligned(dev_w, 16))
+        return fail(GGML_HIP_ERR_INVALID, "w and the Q5_K / Q4_K rows must be 16-byte aligned");
+    ensure_init();
+    HIP_RET(ghip::dequantize_q45_K(qh, dev_wq, K, M, dev_w, resolve_stream(stream)));
+    return GGML_HIP_OK;
+}
+
+int ggml_hip_dequantize_q5_K(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
+    return dequantize_q45k(true, dev_wq, K, M, dev_w, stream);
+}
+
+int ggml_hip_dequantize_q4_K(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
+    return dequantize_q45k(false, dev_wq, K, M, dev_w, stream);
+}
+
+int ggml_hip_mul_mat_q5_K(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N, float *dev_y,
+                          int64_t ldy, int algo, void *stream) {
+    ensure_init();
+    return mul_mat_q45k_dev(gabi::TYPE_Q5_K, dev_w, K, M, dev_x, N, dev_y, ldy, algo, resolve_stream(stream));
+}
+
+int ggml_hip_mul_mat_q4_K(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N, float *dev_y,
+                          int64_t ldy, int algo, void *stream) {
+    ensure_init();
+    return mul_mat_q45k_dev(gabi::TYPE_Q4_K, dev_w, K, M, dev_x, N, dev_y, ldy, algo, resolve_stream(stream));
+}
+
+int ggml_hip_debug_set_q4_K(int on) { return q4k_set_enabled(on); }
+
 /* not in the public header: force the Q8_0 GEMV's launch policy (tests: every policy gives the same y bitwise) */
 int ggml_hip_debug_set_q8_0_gemv_policy(int map, int depth, int wg_per_cu) {
     ghip::gemv_q8_0w_set_policy(map, depth, wg_per_cu);

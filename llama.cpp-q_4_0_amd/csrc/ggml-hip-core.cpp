@@ -437,6 +437,42 @@ int mul_mat_q8_0_dev(const void *w, int64_t K, int64_t M, const float *x, int64_
     return GGML_HIP_OK;
 }
 
+// The Q5_K / Q4_K mul_mat (q45_k.hip; type = gabi::TYPE_Q5_K or TYPE_Q4_K).  Decode and, in this version, prefill
+// too: the fused GEMV, column tiles of 8 above N = 8 (an int8-MFMA GEMM is the follow-up).  Exact mode:
+// the q8_K quantizer into the workspace and the exact kernel, which auto also takes for K > 16384, where the GEMV
+// cannot run (so no shape the hook path accepts fails here).  The blocks are multiples of 16 bytes and the kernels
+// read them as naturally aligned vectors, so W must be 16-byte aligned.
+static constexpr int Q45K_GEMV_MAX_K = 16384;
+int mul_mat_q45k_dev(int type, const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
+                     int algo, hipStream_t s) {
+    if (type != gabi::TYPE_Q5_K && type != gabi::TYPE_Q4_K) return fail(GGML_HIP_ERR_INVALID, "type must be Q5_K or Q4_K");
+    const bool qh = type == gabi::TYPE_Q5_K;
+    if (!w || !x || !y || K <= 0 || M <= 0 || N < 0) return fail(GGML_HIP_ERR_INVALID, "null pointer or bad shape");
+    if (K % QK_K != 0) return fail(GGML_HIP_ERR_INVALID, "K must be a multiple of 256 (QK_K)");
+    if (algo != 0 && algo != 1 && algo != 4) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1 or 4");
+    if (N == 0) return GGML_HIP_OK;
+    if (ldy < M) return fail(GGML_HIP_ERR_INVALID, "ldy < M");
+    if (!aligned(w, 16) || !aligned(x, 16) || !aligned(y, 4))
+        return fail(GGML_HIP_ERR_INVALID, "W and x must be 16-byte, y 4-byte aligned");
+    if (M >= ((int64_t)1 << 31) || N * K >= ((int64_t)1 << 31))
+        return fail(GGML_HIP_ERR_UNSUPPORTED, "matrix too large for 32-bit indices; split rows or columns");
+    const int id = current_device();
+    // auto never fails on K: above the GEMV's limit (one token's q8_K image larger than the LDS; w2 of a 30B / 65B
+    // model has K = 17920 / 22016) it takes the exact kernel, which has no K limit
+    if (algo == 0) algo = (exact_mode() || K > Q45K_GEMV_MAX_K) ? 4 : 1;
+    if (algo == 1) {
+        if (K > Q45K_GEMV_MAX_K) return fail(GGML_HIP_ERR_UNSUPPORTED, "the Q5_K / Q4_K GEMV supports K <= 16384");
+        HIP_RET(ghip::gemv_q45_K(qh, w, K, M, x, N, y, ldy, g_dev[id].info, s));
+        return GGML_HIP_OK;
+    }
+    void *ws = nullptr;
+    const int wrc = stream_workspace(id, s, workspace_bytes_q8k(K, N), &ws);
+    if (wrc != GGML_HIP_OK) return wrc;
+    HIP_RET(ghip::quantize_q8_K(x, K, N, ws, s));
+    HIP_RET(ghip::mm_exact_q45_K(qh, w, K, M, ws, N, y, ldy, s));
+    return GGML_HIP_OK;
+}
+
 // Sibling matrices (one x) that all take k_gemm9 on a registered fp6 image: ONE launch over their
 // row tiles (the x image built once, as before).  The launch plans its tiles (128 x 128 / 128 x 64 /
 // mixed, half tiles) from its own total tile count, which can differ from the per-matrix launches'
@@ -519,6 +555,40 @@ bool supported_mul_mat_q8_0(const tensor *src0, const tensor *src1, const tensor
            dst->type == gabi::TYPE_F32 && src0->ne[0] > 0 && src0->ne[0] % 64 == 0 && src0->ne[0] == src1->ne[0] &&
            dst->ne[0] == src0->ne[1] && dst->ne[1] == src1->ne[1] && src0->ne[2] == src1->ne[2] &&
            src0->ne[3] == src1->ne[3] && is_contiguous(src0) && is_contiguous(src1) && is_contiguous(dst);
+}
+
+// contiguous Q5_K / Q4_K x F32 -> F32 (the layer matrices of a "mostly Q5_K" / "mostly Q4_K" file); predicates of
+// their own for the same reason.  They look at the operands only: the hook path asks q4k_enabled() beside
+// supported_mul_mat_q4k wherever it takes a Q4_K tensor (ggml-hip-tensor.cpp)
+static bool supported_mul_mat_k256(int type, const tensor *src0, const tensor *src1, const tensor *dst) {
+    return src0 && src1 && dst && src0->type == type && src1->type == gabi::TYPE_F32 &&
+           dst->type == gabi::TYPE_F32 && src0->ne[0] > 0 && src0->ne[0] % QK_K == 0 && src0->ne[0] == src1->ne[0] &&
+           dst->ne[0] == src0->ne[1] && dst->ne[1] == src1->ne[1] && src0->ne[2] == src1->ne[2] &&
+           src0->ne[3] == src1->ne[3] && is_contiguous(src0) && is_contiguous(src1) && is_contiguous(dst);
+}
+bool supported_mul_mat_q5k(const tensor *src0, const tensor *src1, const tensor *dst) {
+    return supported_mul_mat_k256(gabi::TYPE_Q5_K, src0, src1, dst);
+}
+bool supported_mul_mat_q4k(const tensor *src0, const tensor *src1, const tensor *dst) {
+    return supported_mul_mat_k256(gabi::TYPE_Q4_K, src0, src1, dst);
+}
+
+// Q4_K on the hook path is opt-in: GGML_HIP_Q4_K=1 or ggml_hip_debug_set_q4_K
+std::atomic<int> g_q4k{-1};
+bool q4k_enabled() {
+    int v = g_q4k.load(std::memory_order_relaxed);
+    if (v < 0) {
+        const char *e = getenv("GGML_HIP_Q4_K");
+        int want = (e && atoi(e) != 0) ? 1 : 0, expect = -1;
+        g_q4k.compare_exchange_strong(expect, want);
+        v = g_q4k.load(std::memory_order_relaxed);
+    }
+    return v != 0;
+}
+int q4k_set_enabled(int on) {
+    const int prev = q4k_enabled() ? 1 : 0;
+    g_q4k.store(on ? 1 : 0, std::memory_order_relaxed);
+    return prev;
 }
 
 [[noreturn]] void op_abort(const tensor *t, const char *why) {

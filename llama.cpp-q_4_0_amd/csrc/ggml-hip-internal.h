@@ -171,6 +171,13 @@ int q8_0_gemm_min_n();
 int q8_0_set_gemm_min_n(int n);                         // -1: the environment value or the default; returns the previous
 int mul_mat_q8_0_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
                      hipStream_t s);
+// the Q5_K / Q4_K mul_mat (type = gabi::TYPE_Q5_K or TYPE_Q4_K): algo 0 auto (4 in exact mode and for K > 16384, else 1), 1 GEMV
+// (column tiles of 8), 4 exact; w 16-byte aligned
+int mul_mat_q45k_dev(int type, const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
+                     int algo, hipStream_t s);
+// the hook path takes Q4_K tensors only with this switch on (GGML_HIP_Q4_K=1 / ggml_hip_debug_set_q4_K; default off)
+bool q4k_enabled();
+int q4k_set_enabled(int on);                            // returns the previous value (0 / 1)
 // true when ggml_hip_mul_mat_q4_0_multi runs these n siblings at N tokens as ONE k_gemm9 launch on registered
 // fp6 images (mul_mat_group_g9 for n > 1, mul_mat_dev's image GEMM for n = 1); img[i] = the images
 bool g9_images(int n, const void *const *w, const int64_t *M, int64_t K, int64_t N, const void **img);
@@ -182,6 +189,8 @@ void split_range(int64_t nrows, int id, int64_t *lo, int64_t *hi);
 bool supported_mul_mat(const tensor *src0, const tensor *src1, const tensor *dst);
 bool supported_mul_mat_q6k(const tensor *src0, const tensor *src1, const tensor *dst);
 bool supported_mul_mat_q8_0(const tensor *src0, const tensor *src1, const tensor *dst);
+bool supported_mul_mat_q5k(const tensor *src0, const tensor *src1, const tensor *dst);
+bool supported_mul_mat_q4k(const tensor *src0, const tensor *src1, const tensor *dst);   // operands only, not the switch
 [[noreturn]] void op_abort(const tensor *t, const char *why);
 inline bool same_shape(const tensor *a, const tensor *b) {
     return a->ne[0] == b->ne[0] && a->ne[1] == b->ne[1] && a->ne[2] == b->ne[2] && a->ne[3] == b->ne[3];

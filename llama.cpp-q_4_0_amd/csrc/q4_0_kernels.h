@@ -169,6 +169,19 @@ hipError_t mm_exact_q8_0w(const void *W, int64_t K, int64_t M, const int8_t *xqs
 // prefill: the k_gemm8 weight image (gemm8_w_bytes(K, M) bytes) from Q8_0 rows; then gemm8_prep_x + gemm8_run
 hipError_t gemm8_prep_w_q8_0(const void *W, int64_t K, int64_t M, void *wws, hipStream_t s);
 
+// Q5_K / Q4_K (q45_k.hip): the layer matrices of a "mostly Q5_K" / "mostly Q4_K" file.  W: ggml block_q5_K
+// (176 bytes per 256 weights) or block_q4_K (144 bytes) rows, verbatim, 16-byte aligned; qh: true Q5_K, false Q4_K.
+constexpr int Q5KB = 176;     // sizeof(block_q5_K)
+constexpr int Q4KB = 144;     // sizeof(block_q4_K)
+// dequantize_row_q5_K / dequantize_row_q4_K, bit-exact
+hipError_t dequantize_q45_K(bool qh, const void *wq, int64_t K, int64_t M, float *w, hipStream_t s);
+// fused q8_K quantize of x (LDS) + q.q8_K GEMV; K % 256 == 0, K <= 16384; N > 8 runs column tiles of 8
+hipError_t gemv_q45_K(bool qh, const void *W, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
+                      const DeviceInfo &dev, hipStream_t s);
+// exact mode: y bit-identical to the AVX2 ggml_vec_dot_q5_K_q8_K / _q4_K_q8_K on the pre-quantized xq8k; any N
+hipError_t mm_exact_q45_K(bool qh, const void *W, int64_t K, int64_t M, const void *xq8k, int64_t N, float *y,
+                          int64_t ldy, hipStream_t s);
+
 // Multi-GPU helper: y[n*ldy + row0[r] + i] = slab[r][n][i] for i < rows[r] (gather compaction).
 // row_begin travels as a kernel argument (no host->device copy, capture-safe)
 static constexpr int SCATTER_MAX_RANKS = 256;

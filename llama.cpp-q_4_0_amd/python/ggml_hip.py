@@ -62,6 +62,11 @@ def _bind(L):
         "ggml_hip_debug_set_q6k_gemm_min_n": ([i32], i32),
         "ggml_hip_dequantize_q8_0": ([vp, i64, i64, vp, vp], i32),
         "ggml_hip_mul_mat_q8_0": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
+        "ggml_hip_dequantize_q5_K": ([vp, i64, i64, vp, vp], i32),
+        "ggml_hip_dequantize_q4_K": ([vp, i64, i64, vp, vp], i32),
+        "ggml_hip_mul_mat_q5_K": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
+        "ggml_hip_mul_mat_q4_K": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
+        "ggml_hip_debug_set_q4_K": ([i32], i32),
         "ggml_hip_debug_q8_0_auto_algo": ([i64, i64, i64], i32),
         "ggml_hip_debug_set_q8_0_gemm_min_n": ([i32], i32),
         "ggml_hip_reserve_workspace": ([i64, i64], i32),
@@ -283,6 +288,28 @@ def mul_mat_q8_0(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_
                                        M if ldy is None else ldy, algo, stream), "mul_mat_q8_0")
 
 
+def dequantize_q5_K(wq_dev, K, M, w_dev, stream=None):
+    check(load().ggml_hip_dequantize_q5_K(_ptr(wq_dev), K, M, _ptr(w_dev), stream), "dequantize_q5_K")
+
+
+def dequantize_q4_K(wq_dev, K, M, w_dev, stream=None):
+    check(load().ggml_hip_dequantize_q4_K(_ptr(wq_dev), K, M, _ptr(w_dev), stream), "dequantize_q4_K")
+
+
+def mul_mat_q5_K(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_off=0, x_off=0, y_off=0):
+    """Q5_K rows (176 * K / 256 bytes each, 16-byte aligned) x f32 [N][K] -> f32 y[n * ldy + m]; algo 0 auto (exact
+    mode or K > 16384: 4; else 1), 1 GEMV (column tiles of 8, K <= 16384), 4 exact."""
+    check(load().ggml_hip_mul_mat_q5_K(_ptr(w_dev) + w_off, K, M, _ptr(x_dev) + x_off, N, _ptr(y_dev) + y_off,
+                                       M if ldy is None else ldy, algo, stream), "mul_mat_q5_K")
+
+
+def mul_mat_q4_K(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_off=0, x_off=0, y_off=0):
+    """Q4_K rows (144 * K / 256 bytes each, 16-byte aligned) x f32 [N][K] -> f32 y[n * ldy + m]; algos as
+    mul_mat_q5_K.  Always available here; the tensor hook path takes Q4_K only with ggml_hip_debug_set_q4_K(1)."""
+    check(load().ggml_hip_mul_mat_q4_K(_ptr(w_dev) + w_off, K, M, _ptr(x_dev) + x_off, N, _ptr(y_dev) + y_off,
+                                       M if ldy is None else ldy, algo, stream), "mul_mat_q4_K")
+
+
 class ChainTask(ctypes.Structure):
     """struct ggml_hip_chain_task (include/ggml-hip.h)"""
     _fields_ = [("nmat", ctypes.c_int), ("K", ctypes.c_int64), ("x", ctypes.c_void_p),
@@ -396,6 +423,7 @@ class Graph:
 GGML_TYPE_F32, GGML_TYPE_Q4_0 = 0, 2
 GGML_TYPE_Q6_K = 14
 GGML_TYPE_Q8_0 = 8
+GGML_TYPE_Q4_K, GGML_TYPE_Q5_K = 12, 13
 GGML_BACKEND_CPU, GGML_BACKEND_GPU, GGML_BACKEND_GPU_SPLIT = 0, 10, 20
 GGML_OP_MUL_MAT = 32
 GGML_TASK_INIT, GGML_TASK_COMPUTE, GGML_TASK_FINALIZE = 0, 1, 2
@@ -439,6 +467,9 @@ def make_tensor(gtype, ne, data=None, backend=GGML_BACKEND_CPU):
     elif gtype == GGML_TYPE_Q8_0:
         t.nb[0] = 34
         t.nb[1] = 34 * ne[0] // 32
+    elif gtype in (GGML_TYPE_Q5_K, GGML_TYPE_Q4_K):
+        t.nb[0] = 176 if gtype == GGML_TYPE_Q5_K else 144
+        t.nb[1] = t.nb[0] * ne[0] // 256
     else:
         t.nb[0] = 4
         t.nb[1] = 4 * ne[0]
