@@ -206,15 +206,25 @@ int ggml_hip_debug_set_q8_0_gemm_min_n(int n);
  * dequantize_q5_K / _q4_K: dequantize_row_q5_K (k_quants.c:926-969) / dequantize_row_q4_K (733-770), bit-exact. */
 int ggml_hip_dequantize_q5_K(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream);
 int ggml_hip_dequantize_q4_K(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream);
-/* y[n * ldy + m], ldy >= M.  algo: 0 auto (4 in exact mode and for K > 16384, else 1), 1 GEMV (K <= 16384) with the q8_K
- * quantization of x fused in, exact int32 superblock sums and one fixed fp32 order per superblock (column tiles of
- * 8 for N > 8, bitwise the per-tile calls; y does not depend on the launch geometry), 4 exact: bit-identical to the
- * AVX2 branch of ggml_vec_dot_q5_K_q8_K (k_quants.c:2927-3010) / ggml_vec_dot_q4_K_q8_K (2450-2513).  Anything
- * else -> GGML_HIP_ERR_INVALID. */
+/* y[n * ldy + m], ldy >= M.  algo: 0 auto (4 in exact mode and for K > 16384; else 6 when N >= the GEMM threshold;
+ * else 1), 1 GEMV (K <= 16384) with the q8_K quantization of x fused in, exact int32 superblock sums and one fixed
+ * fp32 order per superblock (column tiles of 8 for N > 8, bitwise the per-tile calls; y does not depend on the
+ * launch geometry), 4 exact: bit-identical to the AVX2 branch of ggml_vec_dot_q5_K_q8_K (k_quants.c:2927-3010) /
+ * ggml_vec_dot_q4_K_q8_K (2450-2513), 6 prefill GEMM on the int8 matrix cores (any K % 256 == 0): the blocks read
+ * in place, x quantized to q8_K into the workspace (covered by ggml_hip_reserve_workspace(K, N)); every y bit for
+ * bit algo 1's (the same exact integer superblock sums and the same fp32 step per superblock, in order), so the
+ * auto switch between 1 and 6 never changes a result.  Anything else (2, 3 and 5 included) -> GGML_HIP_ERR_INVALID. */
 int ggml_hip_mul_mat_q5_K(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N,
                           float *dev_y, int64_t ldy, int algo, void *stream);
 int ggml_hip_mul_mat_q4_K(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N,
                           float *dev_y, int64_t ldy, int algo, void *stream);
+/* debug, no device needed: the algo that algo 0 of ggml_hip_mul_mat_q5_K / _q4_K (type = GGML_TYPE_Q5_K 13 /
+ * GGML_TYPE_Q4_K 12) would run now: 1, 4 or 6; a bad type or K -> GGML_HIP_ERR_INVALID */
+int ggml_hip_debug_q45k_auto_algo(int type, int64_t K, int64_t M, int64_t N);
+/* debug: the smallest N at which auto takes the GEMM, one value for both types (default 32: the measured crossover;
+ * GGML_HIP_Q45K_GEMM_MIN_N; values below 9 count as 9); -1 restores the environment value or the default.  Returns
+ * the previous value. */
+int ggml_hip_debug_set_q45k_gemm_min_n(int n);
 /* the hook path (can_mul_mat, transform_tensor, compute_forward, ggml_hip_mul_mat) takes GGML_TYPE_Q4_K tensors
  * only while this switch is on; off by default (or GGML_HIP_Q4_K=1 in the environment).  Returns the previous
  * value (0 / 1).  Tensors uploaded while it was on stay on the device, keep being served by

@@ -120,6 +120,14 @@ int ggml_hip_mul_mat_q4_K(const void *dev_w, int64_t K, int64_t M, const float *
     return mul_mat_q45k_dev(gabi::TYPE_Q4_K, dev_w, K, M, dev_x, N, dev_y, ldy, algo, resolve_stream(stream));
 }
 
+int ggml_hip_debug_q45k_auto_algo(int type, int64_t K, int64_t M, int64_t N) {
+    if (type != gabi::TYPE_Q5_K && type != gabi::TYPE_Q4_K) return fail(GGML_HIP_ERR_INVALID, "type must be Q5_K or Q4_K");
+    if (K <= 0 || K % QK_K || M <= 0 || N < 0) return fail(GGML_HIP_ERR_INVALID, "bad shape");
+    return q45k_auto_algo(K, M, N);
+}
+
+int ggml_hip_debug_set_q45k_gemm_min_n(int n) { return q45k_set_gemm_min_n(n); }
+
 int ggml_hip_debug_set_q4_K(int on) { return q4k_set_enabled(on); }
 
 /* not in the public header: force the Q8_0 GEMV's launch policy (tests: every policy gives the same y bitwise) */

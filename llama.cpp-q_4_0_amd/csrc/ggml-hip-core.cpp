@@ -437,19 +437,59 @@ int mul_mat_q8_0_dev(const void *w, int64_t K, int64_t M, const float *x, int64_
     return GGML_HIP_OK;
 }
 
-// The Q5_K / Q4_K mul_mat (q45_k.hip; type = gabi::TYPE_Q5_K or TYPE_Q4_K).  Decode and, in this version, prefill
-// too: the fused GEMV, column tiles of 8 above N = 8 (an int8-MFMA GEMM is the follow-up).  Exact mode:
-// the q8_K quantizer into the workspace and the exact kernel, which auto also takes for K > 16384, where the GEMV
-// cannot run (so no shape the hook path accepts fails here).  The blocks are multiples of 16 bytes and the kernels
-// read them as naturally aligned vectors, so W must be 16-byte aligned.
+// The Q5_K / Q4_K mul_mat (q45_k.hip, q45_k_gemm.hip; type = gabi::TYPE_Q5_K or TYPE_Q4_K).  Decode: the fused
+// GEMV (column tiles of 8 above N = 8).  Prefill: the q8_K values of x as planes in the stream's workspace and the
+// int8-MFMA GEMM k_gemm_q45_K (algo 6; 5 stays invalid for these types), whose y is bit for bit the GEMV's (the
+// same exact integer superblock sums, the same fp32 step per superblock in the same order), so the switch between
+// the two never changes a result.  Exact mode: the q8_K quantizer into the workspace and the exact kernel, which
+// auto also takes for K > 16384, where the GEMV cannot run (so no shape the hook path accepts fails here, and a
+// long K computes what it did before the GEMM existed).  Auto takes the GEMM from N >= q45k_gemm_min_n()
+// (tools/q45k_gemm_bench.py; GGML_HIP_Q45K_GEMM_MIN_N / ggml_hip_debug_set_q45k_gemm_min_n, never
+// below 9).  The blocks are multiples of 16 bytes and the kernels read them as naturally aligned vectors, so W
+// must be 16-byte aligned.
+// qs int8 [N][K] + dig int8 [N][K / 256][16] + d f32 [N][K / 256]: 256 + 20 bytes per 256 elements against the 288
+// of workspace_bytes(K, N) behind the same padding of qs, so never more than ggml_hip_reserve_workspace reserves
+static size_t q45k_dig_offset(int64_t K, int64_t N) { return (size_t)(N * K + 255) & ~(size_t)255; }
+size_t workspace_bytes_q45k_gemm(int64_t K, int64_t N) {
+    return q45k_dig_offset(K, N) + (size_t)N * (size_t)(K / QK_K) * 20;
+}
+
+// the sweep (profiles/q45k_gemm.json; 4096 -> 4096, 4096 -> 11008, 11008 -> 4096, weights from memory): the GEMM's
+// time is flat in N up to 128 (Q5_K: 51 / 52 / 129 us at N = 9), so the tiled GEMV wins at N = 9 on 4096 -> 4096 and
+// 11008 -> 4096 (33 and 86 us) and ties at N = 16 on Q5_K 4096 -> 4096 (50.8 against 51.6 us); from N = 32 the GEMM
+// wins on every shape of both types (Q5_K 4096 -> 4096: 52.5 against 99.6 us).  One threshold: the types' crossovers
+// do not differ.
+static constexpr int Q45K_GEMM_MIN_N = 32;
 static constexpr int Q45K_GEMV_MAX_K = 16384;
+std::atomic<int> g_q45k_min_n{-1};
+int q45k_gemm_min_n() {
+    int v = g_q45k_min_n.load(std::memory_order_relaxed);
+    if (v < 0) {
+        const char *e = getenv("GGML_HIP_Q45K_GEMM_MIN_N");
+        int want = e ? atoi(e) : Q45K_GEMM_MIN_N, expect = -1;
+        if (want < 9) want = 9;
+        g_q45k_min_n.compare_exchange_strong(expect, want);
+        v = g_q45k_min_n.load(std::memory_order_relaxed);
+    }
+    return v;
+}
+int q45k_set_gemm_min_n(int n) {
+    const int prev = q45k_gemm_min_n();
+    g_q45k_min_n.store(n < 0 ? -1 : (n < 9 ? 9 : n), std::memory_order_relaxed);    // -1: re-read the environment
+    return prev;
+}
+int q45k_auto_algo(int64_t K, int64_t, int64_t N) {
+    if (exact_mode() || K > Q45K_GEMV_MAX_K) return 4;
+    return N >= q45k_gemm_min_n() ? 6 : 1;
+}
+
 int mul_mat_q45k_dev(int type, const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
                      int algo, hipStream_t s) {
     if (type != gabi::TYPE_Q5_K && type != gabi::TYPE_Q4_K) return fail(GGML_HIP_ERR_INVALID, "type must be Q5_K or Q4_K");
     const bool qh = type == gabi::TYPE_Q5_K;
     if (!w || !x || !y || K <= 0 || M <= 0 || N < 0) return fail(GGML_HIP_ERR_INVALID, "null pointer or bad shape");
     if (K % QK_K != 0) return fail(GGML_HIP_ERR_INVALID, "K must be a multiple of 256 (QK_K)");
-    if (algo != 0 && algo != 1 && algo != 4) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1 or 4");
+    if (algo != 0 && algo != 1 && algo != 4 && algo != 6) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1, 4 or 6");
     if (N == 0) return GGML_HIP_OK;
     if (ldy < M) return fail(GGML_HIP_ERR_INVALID, "ldy < M");
     if (!aligned(w, 16) || !aligned(x, 16) || !aligned(y, 4))
@@ -459,13 +499,24 @@ int mul_mat_q45k_dev(int type, const void *w, int64_t K, int64_t M, const float 
     const int id = current_device();
     // auto never fails on K: above the GEMV's limit (one token's q8_K image larger than the LDS; w2 of a 30B / 65B
     // model has K = 17920 / 22016) it takes the exact kernel, which has no K limit
-    if (algo == 0) algo = (exact_mode() || K > Q45K_GEMV_MAX_K) ? 4 : 1;
+    if (algo == 0) algo = q45k_auto_algo(K, M, N);
     if (algo == 1) {
         if (K > Q45K_GEMV_MAX_K) return fail(GGML_HIP_ERR_UNSUPPORTED, "the Q5_K / Q4_K GEMV supports K <= 16384");
         HIP_RET(ghip::gemv_q45_K(qh, w, K, M, x, N, y, ldy, g_dev[id].info, s));
         return GGML_HIP_OK;
     }
     void *ws = nullptr;
+    if (algo == 6) {
+        if (((M + 63) / 64) * ((N + 63) / 64) >= ((int64_t)1 << 31))
+            return fail(GGML_HIP_ERR_UNSUPPORTED, "too many tiles for one grid; split rows or columns");
+        const int wrc = stream_workspace(id, s, workspace_bytes_q45k_gemm(K, N), &ws);
+        if (wrc != GGML_HIP_OK) return wrc;
+        void *dig = (char *)ws + q45k_dig_offset(K, N);
+        float *xd = (float *)((char *)dig + (size_t)N * (size_t)(K / QK_K) * 16);
+        HIP_RET(ghip::quantize_q8_K_digit_planes(x, K, N, ws, xd, dig, s));
+        HIP_RET(ghip::gemm_q45_K(qh, w, K, M, ws, xd, dig, N, y, ldy, g_dev[id].info, s));
+        return GGML_HIP_OK;
+    }
     const int wrc = stream_workspace(id, s, workspace_bytes_q8k(K, N), &ws);
     if (wrc != GGML_HIP_OK) return wrc;
     HIP_RET(ghip::quantize_q8_K(x, K, N, ws, s));

@@ -171,8 +171,12 @@ int q8_0_gemm_min_n();
 int q8_0_set_gemm_min_n(int n);                         // -1: the environment value or the default; returns the previous
 int mul_mat_q8_0_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
                      hipStream_t s);
-// the Q5_K / Q4_K mul_mat (type = gabi::TYPE_Q5_K or TYPE_Q4_K): algo 0 auto (4 in exact mode and for K > 16384, else 1), 1 GEMV
-// (column tiles of 8), 4 exact; w 16-byte aligned
+// the Q5_K / Q4_K mul_mat (type = gabi::TYPE_Q5_K or TYPE_Q4_K): algo 0 auto (q45k_auto_algo), 1 GEMV (column tiles
+// of 8), 4 exact, 6 int8-MFMA GEMM; w 16-byte aligned
+size_t workspace_bytes_q45k_gemm(int64_t K, int64_t N);
+int q45k_auto_algo(int64_t K, int64_t M, int64_t N);    // what algo 0 runs now: 1, 4 or 6 (no device needed)
+int q45k_gemm_min_n();
+int q45k_set_gemm_min_n(int n);                         // -1: the environment value or the default; returns the previous
 int mul_mat_q45k_dev(int type, const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
                      int algo, hipStream_t s);
 // the hook path takes Q4_K tensors only with this switch on (GGML_HIP_Q4_K=1 / ggml_hip_debug_set_q4_K; default off)

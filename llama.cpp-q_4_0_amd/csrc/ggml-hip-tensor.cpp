@@ -96,7 +96,8 @@ namespace ghh {
 std::mutex g_host_copy_mu;
 std::unordered_map<const void *, void *> g_host_copies;
 
-// The k-quant layer types of q45_k.hip as the hook path takes them: Q5_K always, Q4_K only with its switch on
+// The k-quant layer types of q45_k.hip / q45_k_gemm.hip as the hook path takes them (always with algo 0: the GEMV,
+// from N >= q45k_gemm_min_n() the GEMM, bitwise the same y): Q5_K always, Q4_K only with its switch on
 // (q4k_enabled(): GGML_HIP_Q4_K=1 / ggml_hip_debug_set_q4_K).  With the switch off every entry
 // point below treats a host-resident Q4_K tensor as a type no device op reads.  A Q4_K weight that
 // transform_tensor uploaded while the switch was on keeps being served after it is turned off: its data is on

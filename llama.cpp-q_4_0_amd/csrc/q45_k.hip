@@ -1,6 +1,7 @@
 // q45_k.hip — the Q5_K / Q4_K x F32 mul_mat of a "mostly Q5_K" / "mostly Q4_K" file's layer matrices (gfx950,
 // wave64): the dequantizer, the fused GEMV (N <= 8 per launch) and the exact kernel, one template parameter QH
-// (true: Q5_K, false: Q4_K).  Shared device helpers: q4_0_device.h, q6_k_device.h (q8k_block_lane).  What each
+// (true: Q5_K, false: Q4_K); the prefill GEMM is q45_k_gemm.hip.  Shared device helpers: q4_0_device.h,
+// q6_k_device.h (q8k_block_lane), q45_k_device.h (Q45<QH>, unpack_scales_k4).  What each
 // kernel restates (reference = k_quants.c of Fcucgvhhhvjv/llama.cpp-q_4_0, QK_K = 256):
 //   k_dequantize_q45_K<QH>  dequantize_row_q4_K k_quants.c:733-770 / dequantize_row_q5_K 926-969 (bit-exact)
 //   k_gemv_q45_K<QH, NT>    ggml_vec_dot_q4_K_q8_K / _q5_K_q8_K with the q8_K quantization of x fused into the
@@ -22,31 +23,11 @@
 //   t_b = fma(d_x d, (float)isum_b, -((d_x dmin) (float)msum_b))      (d_x d and d_x dmin: one rounded multiply each)
 //   acc = acc + t_b,  b = 0, 1, ..., K / 256 - 1, K never split
 // so y does not depend on the grid, the row mapping or the token tile, and x -> 2x doubles every term exactly.
-#include "q6_k_device.h"
+#include "q45_k_device.h"
 
 #include <atomic>
 
 namespace ghip {
-
-template <bool QH>
-struct Q45 {
-    static constexpr int BYTES = QH ? Q5KB : Q4KB;
-    static constexpr int QS = QH ? 48 : 16;                // byte offset of qs[128]
-};
-
-// the 6-bit scales and mins of one superblock from its three scale dwords (k_quants.c:2462-2467): bytes of
-// sc_lo | sc_hi are sc[0..3] | sc[4..7], bytes of m_lo | m_hi are m[0..3] | m[4..7]
-struct ScaleMin {
-    uint32_t sc_lo, sc_hi, m_lo, m_hi;
-};
-__device__ __forceinline__ ScaleMin unpack_scales_k4(uint32_t s0, uint32_t s1, uint32_t s2) {
-    ScaleMin r;
-    r.m_hi = ((s2 >> 4) & 0x0F0F0F0Fu) | (((s1 >> 6) & 0x03030303u) << 4);
-    r.m_lo = s1 & 0x3F3F3F3Fu;
-    r.sc_hi = (s2 & 0x0F0F0F0Fu) | (((s0 >> 6) & 0x03030303u) << 4);
-    r.sc_lo = s0 & 0x3F3F3F3Fu;
-    return r;
-}
 
 // ---------------------------------------------------------------------------------------------
 // block rows -> f32; one thread per four consecutive elements (one sub-block): d1 * (float)q - m1 with

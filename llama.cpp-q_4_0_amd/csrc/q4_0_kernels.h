@@ -181,6 +181,13 @@ hipError_t gemv_q45_K(bool qh, const void *W, int64_t K, int64_t M, const float 
 // exact mode: y bit-identical to the AVX2 ggml_vec_dot_q5_K_q8_K / _q4_K_q8_K on the pre-quantized xq8k; any N
 hipError_t mm_exact_q45_K(bool qh, const void *W, int64_t K, int64_t M, const void *xq8k, int64_t N, float *y,
                           int64_t ldy, hipStream_t s);
+// prefill (q45_k_gemm.hip): the q8_K values of x as planes, qs int8 [N][K] + d f32 [N][K / 256] + dig int8
+// [N][K / 256][16] (the low then the high base-128 digits of the eight per-32 sums; qs and dig 16-byte aligned), and
+// the int8-MFMA GEMM on them, y bitwise gemv_q45_K's; any K % 256 == 0 (N K < 2^31), M, N >= 1
+hipError_t quantize_q8_K_digit_planes(const float *x, int64_t K, int64_t N, void *qs, float *xd, void *dig,
+                                      hipStream_t s);
+hipError_t gemm_q45_K(bool qh, const void *W, int64_t K, int64_t M, const void *xqs, const float *xd, const void *xdig,
+                      int64_t N, float *y, int64_t ldy, const DeviceInfo &dev, hipStream_t s);
 
 // Multi-GPU helper: y[n*ldy + row0[r] + i] = slab[r][n][i] for i < rows[r] (gather compaction).
 // row_begin travels as a kernel argument (no host->device copy, capture-safe)

@@ -67,6 +67,8 @@ def _bind(L):
         "ggml_hip_mul_mat_q5_K": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
         "ggml_hip_mul_mat_q4_K": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
         "ggml_hip_debug_set_q4_K": ([i32], i32),
+        "ggml_hip_debug_q45k_auto_algo": ([i32, i64, i64, i64], i32),
+        "ggml_hip_debug_set_q45k_gemm_min_n": ([i32], i32),
         "ggml_hip_debug_q8_0_auto_algo": ([i64, i64, i64], i32),
         "ggml_hip_debug_set_q8_0_gemm_min_n": ([i32], i32),
         "ggml_hip_reserve_workspace": ([i64, i64], i32),
@@ -298,7 +300,8 @@ def dequantize_q4_K(wq_dev, K, M, w_dev, stream=None):
 
 def mul_mat_q5_K(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_off=0, x_off=0, y_off=0):
     """Q5_K rows (176 * K / 256 bytes each, 16-byte aligned) x f32 [N][K] -> f32 y[n * ldy + m]; algo 0 auto (exact
-    mode or K > 16384: 4; else 1), 1 GEMV (column tiles of 8, K <= 16384), 4 exact."""
+    mode or K > 16384: 4; N below the GEMM threshold: 1; else 6), 1 GEMV (column tiles of 8, K <= 16384), 4 exact,
+    6 int8-MFMA GEMM (bitwise algo 1)."""
     check(load().ggml_hip_mul_mat_q5_K(_ptr(w_dev) + w_off, K, M, _ptr(x_dev) + x_off, N, _ptr(y_dev) + y_off,
                                        M if ldy is None else ldy, algo, stream), "mul_mat_q5_K")
 
@@ -308,6 +311,18 @@ def mul_mat_q4_K(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_
     mul_mat_q5_K.  Always available here; the tensor hook path takes Q4_K only with ggml_hip_debug_set_q4_K(1)."""
     check(load().ggml_hip_mul_mat_q4_K(_ptr(w_dev) + w_off, K, M, _ptr(x_dev) + x_off, N, _ptr(y_dev) + y_off,
                                        M if ldy is None else ldy, algo, stream), "mul_mat_q4_K")
+
+
+def debug_q45k_auto_algo(gtype, K, M, N):
+    """The algo that algo 0 of mul_mat_q5_K / mul_mat_q4_K (gtype = GGML_TYPE_Q5_K / GGML_TYPE_Q4_K) would run now:
+    1, 4 or 6; no device needed."""
+    return load().ggml_hip_debug_q45k_auto_algo(gtype, K, M, N)
+
+
+def debug_set_q45k_gemm_min_n(n):
+    """The smallest N at which auto takes the Q5_K / Q4_K GEMM (below 9 counts as 9; -1: the environment value or
+    the default); returns the previous value."""
+    return load().ggml_hip_debug_set_q45k_gemm_min_n(n)
 
 
 class ChainTask(ctypes.Structure):
