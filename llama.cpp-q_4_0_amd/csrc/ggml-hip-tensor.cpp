@@ -81,7 +81,9 @@ void assign_buffers_impl(tensor *t, bool scratch, bool force_inplace) {
     } else {
         void *p = nullptr;
         HIP_FATAL(hipMalloc(&p, size ? size : 1));
-        HIP_FATAL(GHIP_SYNC(hipMemset)(p, 0, size));
+        // zeroed on the backend's stream, which is non-blocking: a hipMemset on the null stream is not ordered
+        // against it and could land after the first node that writes the buffer
+        HIP_FATAL(GHIP_SYNC(hipMemsetAsync)(p, 0, size, g_dev[id].stream));
         own_device_buffer(p);
         extra->data_device[id] = p;
     }

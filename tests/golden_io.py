@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-_DT = {"u8": np.uint8, "f32": np.float32, "i64": np.int64}
+_DT = {"u8": np.uint8, "u16": np.uint16, "f32": np.float32, "i64": np.int64}
 
 
 def manifest(variant):

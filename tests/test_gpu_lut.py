@@ -3,8 +3,10 @@ device (csrc/q4_0_device.h lut_silu / lut_exp): the backend checks the direct ev
 tables over every finite fp16 input when it builds them, and only then tags the kernels' table pointers for
 direct evaluation.  Here: the check found no difference on this MI355X (every one of the 63,488 finite inputs
 of each table reproduced bit for bit), and the silu consumers give bitwise the same outputs with gathers and
-with direct evaluation.  The ops stay pinned against the reference's CPU ops end to end in exact mode
-(tests/test_gpu_llama_ggjt.py, tests/test_gpu_ggml_hook.py)."""
+with direct evaluation.  The ops themselves (silu, soft_max and the chains that use the tables) are pinned bit for
+bit against the restatement of ggml.c's CPU ops, one op and one chain at a time (tests/test_gpu_ops_ref.py,
+tests/test_gpu_chains_ref.py), and end to end in exact mode (tests/test_gpu_llama_ggjt.py,
+tests/test_gpu_ggml_hook.py)."""
 import ctypes
 
 import numpy as np

@@ -4,7 +4,8 @@ the two-pairs-per-thread form (16-byte rows and (cos, sin) rows; the K-cache val
 store when four share a contiguous target row) and the one-pair form it falls back to (a row start off 16
 bytes), a cache view off the packed-store alignment, a target row length that is no multiple of 4, F16
 and F32 targets, decode and prefill token counts, a partial rotation (n_dims < ne0).  The rotation
-itself against numpy (float64 angles) within 2e-5 of the value scale."""
+itself against numpy (float64 angles) within 2e-5 of the value scale here; the rope node's own kernel is
+bitwise ggml.c's mode-0 rope as tests/ggml_ops_ref.py restates it (tests/test_gpu_ops_ref.py::test_rope)."""
 import ctypes
 
 import numpy as np
