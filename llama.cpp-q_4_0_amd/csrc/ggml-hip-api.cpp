@@ -49,84 +49,88 @@ int ggml_hip_quantize_q8_K(const float *dev_x, int64_t K, int64_t N, void *dev_x
     return GGML_HIP_OK;
 }
 
+// the weight types with a row in weight_type()'s table: one argument check for their dequantizers, one body for
+// their mul_mats and for what algo 0 would run
+static int check_dequantize(int type, const void *dev_wq, int64_t K, int64_t M, const float *dev_w) {
+    const WeightType &t = *weight_type(type);
+    if (!dev_w || !dev_wq || K <= 0 || K % t.dq_granule || M < 0) return fail(GGML_HIP_ERR_INVALID, "bad arguments");
+    if (!aligned(dev_wq, t.dq_align) || !aligned(dev_w, 16)) return fail(GGML_HIP_ERR_INVALID, t.err_dq_align);
+    return GGML_HIP_OK;
+}
+
+static int mul_mat_type(int type, const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N, float *dev_y,
+                        int64_t ldy, int algo, void *stream) {
+    ensure_init();
+    return weight_type(type)->run(dev_w, K, M, dev_x, N, dev_y, ldy, algo, resolve_stream(stream));
+}
+
+static int debug_auto_algo(int type, int64_t K, int64_t M, int64_t N) {
+    const WeightType &t = *weight_type(type);
+    if (K <= 0 || K % t.k_granule || M <= 0 || N < 0) return fail(GGML_HIP_ERR_INVALID, "bad shape");
+    return auto_algo(t, K, N);
+}
+
 int ggml_hip_dequantize_q6_K(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
-    if (!dev_w || !dev_wq || K <= 0 || K % QK_K || M < 0) return fail(GGML_HIP_ERR_INVALID, "bad arguments");
-    if (!aligned(dev_wq, 2) || !aligned(dev_w, 16))
-        return fail(GGML_HIP_ERR_INVALID, "w must be 16-byte aligned, the Q6_K rows 2-byte aligned");
+    if (const int rc = check_dequantize(gabi::TYPE_Q6_K, dev_wq, K, M, dev_w); rc != GGML_HIP_OK) return rc;
     HIP_RET(ghip::dequantize_q6_K(dev_wq, K, M, dev_w, resolve_stream(stream)));
     return GGML_HIP_OK;
 }
 
 int ggml_hip_mul_mat_q6_K(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N, float *dev_y,
                           int64_t ldy, int algo, void *stream) {
-    ensure_init();
-    return mul_mat_q6k_dev(dev_w, K, M, dev_x, N, dev_y, ldy, algo, resolve_stream(stream));
+    return mul_mat_type(gabi::TYPE_Q6_K, dev_w, K, M, dev_x, N, dev_y, ldy, algo, stream);
 }
 
-int ggml_hip_debug_q6k_auto_algo(int64_t K, int64_t M, int64_t N) {
-    if (K <= 0 || K % QK_K || M <= 0 || N < 0) return fail(GGML_HIP_ERR_INVALID, "bad shape");
-    return q6k_auto_algo(K, M, N);
-}
+int ggml_hip_debug_q6k_auto_algo(int64_t K, int64_t M, int64_t N) { return debug_auto_algo(gabi::TYPE_Q6_K, K, M, N); }
 
-int ggml_hip_debug_set_q6k_gemm_min_n(int n) { return q6k_set_gemm_min_n(n); }
+int ggml_hip_debug_set_q6k_gemm_min_n(int n) { return weight_type(gabi::TYPE_Q6_K)->min_n->set(n); }
 
 int ggml_hip_dequantize_q8_0(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
-    if (!dev_w || !dev_wq || K <= 0 || K % QK || M < 0) return fail(GGML_HIP_ERR_INVALID, "bad arguments");
-    if (!aligned(dev_wq, 2) || !aligned(dev_w, 16))
-        return fail(GGML_HIP_ERR_INVALID, "w must be 16-byte aligned, the Q8_0 rows 2-byte aligned");
+    if (const int rc = check_dequantize(gabi::TYPE_Q8_0, dev_wq, K, M, dev_w); rc != GGML_HIP_OK) return rc;
     HIP_RET(ghip::dequantize_q8_0(dev_wq, K, M, dev_w, resolve_stream(stream)));
     return GGML_HIP_OK;
 }
 
 int ggml_hip_mul_mat_q8_0(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N, float *dev_y,
                           int64_t ldy, int algo, void *stream) {
-    ensure_init();
-    return mul_mat_q8_0_dev(dev_w, K, M, dev_x, N, dev_y, ldy, algo, resolve_stream(stream));
+    return mul_mat_type(gabi::TYPE_Q8_0, dev_w, K, M, dev_x, N, dev_y, ldy, algo, stream);
 }
 
-int ggml_hip_debug_q8_0_auto_algo(int64_t K, int64_t M, int64_t N) {
-    if (K <= 0 || K % 64 || M <= 0 || N < 0) return fail(GGML_HIP_ERR_INVALID, "bad shape");
-    return q8_0_auto_algo(K, M, N);
-}
+int ggml_hip_debug_q8_0_auto_algo(int64_t K, int64_t M, int64_t N) { return debug_auto_algo(gabi::TYPE_Q8_0, K, M, N); }
 
-int ggml_hip_debug_set_q8_0_gemm_min_n(int n) { return q8_0_set_gemm_min_n(n); }
+int ggml_hip_debug_set_q8_0_gemm_min_n(int n) { return weight_type(gabi::TYPE_Q8_0)->min_n->set(n); }
 
-static int dequantize_q45k(bool qh, const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
-    if (!dev_w || !dev_wq || K <= 0 || K % QK_K || M < 0) return fail(GGML_HIP_ERR_INVALID, "bad arguments");
-    if (!aligned(dev_wq, 16) || !aligned(dev_w, 16))
-        return fail(GGML_HIP_ERR_INVALID, "w and the Q5_K / Q4_K rows must be 16-byte aligned");
+static int dequantize_q45k(int type, const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
+    if (const int rc = check_dequantize(type, dev_wq, K, M, dev_w); rc != GGML_HIP_OK) return rc;
     ensure_init();
-    HIP_RET(ghip::dequantize_q45_K(qh, dev_wq, K, M, dev_w, resolve_stream(stream)));
+    HIP_RET(ghip::dequantize_q45_K(type == gabi::TYPE_Q5_K, dev_wq, K, M, dev_w, resolve_stream(stream)));
     return GGML_HIP_OK;
 }
 
 int ggml_hip_dequantize_q5_K(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
-    return dequantize_q45k(true, dev_wq, K, M, dev_w, stream);
+    return dequantize_q45k(gabi::TYPE_Q5_K, dev_wq, K, M, dev_w, stream);
 }
 
 int ggml_hip_dequantize_q4_K(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
-    return dequantize_q45k(false, dev_wq, K, M, dev_w, stream);
+    return dequantize_q45k(gabi::TYPE_Q4_K, dev_wq, K, M, dev_w, stream);
 }
 
 int ggml_hip_mul_mat_q5_K(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N, float *dev_y,
                           int64_t ldy, int algo, void *stream) {
-    ensure_init();
-    return mul_mat_q45k_dev(gabi::TYPE_Q5_K, dev_w, K, M, dev_x, N, dev_y, ldy, algo, resolve_stream(stream));
+    return mul_mat_type(gabi::TYPE_Q5_K, dev_w, K, M, dev_x, N, dev_y, ldy, algo, stream);
 }
 
 int ggml_hip_mul_mat_q4_K(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N, float *dev_y,
                           int64_t ldy, int algo, void *stream) {
-    ensure_init();
-    return mul_mat_q45k_dev(gabi::TYPE_Q4_K, dev_w, K, M, dev_x, N, dev_y, ldy, algo, resolve_stream(stream));
+    return mul_mat_type(gabi::TYPE_Q4_K, dev_w, K, M, dev_x, N, dev_y, ldy, algo, stream);
 }
 
 int ggml_hip_debug_q45k_auto_algo(int type, int64_t K, int64_t M, int64_t N) {
     if (type != gabi::TYPE_Q5_K && type != gabi::TYPE_Q4_K) return fail(GGML_HIP_ERR_INVALID, "type must be Q5_K or Q4_K");
-    if (K <= 0 || K % QK_K || M <= 0 || N < 0) return fail(GGML_HIP_ERR_INVALID, "bad shape");
-    return q45k_auto_algo(K, M, N);
+    return debug_auto_algo(type, K, M, N);
 }
 
-int ggml_hip_debug_set_q45k_gemm_min_n(int n) { return q45k_set_gemm_min_n(n); }
+int ggml_hip_debug_set_q45k_gemm_min_n(int n) { return weight_type(gabi::TYPE_Q5_K)->min_n->set(n); }
 
 int ggml_hip_debug_set_q4_K(int on) { return q4k_set_enabled(on); }
 

@@ -293,126 +293,172 @@ int mul_mat_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, 
     return GGML_HIP_OK;
 }
 
-// The Q6_K mul_mat (q6_k.hip, q6_k_gemm.hip).  Decode: the fused GEMV (column tiles of 8 above N = 8).  Prefill:
-// the q8_K values of x as planes in the stream's workspace and the int8-MFMA GEMM k_gemm_q6_K, whose y is bit
-// for bit the GEMV's (the same exact integer superblock sums, the same fp32 step per superblock in the same
-// order), so the switch between the two never changes a result.  Exact mode: the q8_K quantizer into the
-// workspace and the exact kernel.  Auto takes the GEMM from N >= q6k_gemm_min_n() (measured crossover,
-// tools/q6k_gemm_bench.py; GGML_HIP_Q6K_GEMM_MIN_N / ggml_hip_debug_set_q6k_gemm_min_n, never
-// below 9) and wherever the GEMV cannot run (K > 16384).
-size_t workspace_bytes_q8k(int64_t K, int64_t N) { return (size_t)N * (size_t)(K / QK_K) * Q8KB; }
-// qs int8 [N][K] + d f32 [N][K / 256]; never more than workspace_bytes(K, N), which ggml_hip_reserve_workspace reserves
-size_t workspace_bytes_q6k_gemm(int64_t K, int64_t N) {
-    return ((size_t)(N * K + 255) & ~(size_t)255) + (size_t)N * (size_t)(K / QK_K) * 4;
-}
+// ------------------------------------------------------------------------------------------
+// The weight types beside Q4_0: one row each (WeightType, ggml-hip-internal.h).  A type's mul_mat has algo 0 auto
+// (auto_algo), 1 the fused GEMV in column tiles, 4 the exact kernel and the type's own GEMM algo; the GEMM's y is
+// bit for bit the GEMV's on the k-quants (the same exact integer superblock sums, the same fp32 step per
+// superblock in the same order), so the switch between the two never changes a result.
 
-// the sweep (profiles/q6k_gemm.json, lm_head shape): the GEMM wins at every swept N from 9, the rule's floor
-static constexpr int Q6K_GEMM_MIN_N = 9;
-static constexpr int Q6K_GEMV_MAX_K = 16384;
-std::atomic<int> g_q6k_min_n{-1};
-int q6k_gemm_min_n() {
-    int v = g_q6k_min_n.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *e = getenv("GGML_HIP_Q6K_GEMM_MIN_N");
-        int want = e ? atoi(e) : Q6K_GEMM_MIN_N, expect = -1;
+int GemmMinN::get() {
+    int n = v.load(std::memory_order_relaxed);
+    if (n < 0) {
+        const char *e = getenv(env);
+        int want = e ? atoi(e) : dflt, expect = -1;
         if (want < 9) want = 9;
-        g_q6k_min_n.compare_exchange_strong(expect, want);
-        v = g_q6k_min_n.load(std::memory_order_relaxed);
+        v.compare_exchange_strong(expect, want);
+        n = v.load(std::memory_order_relaxed);
     }
-    return v;
+    return n;
 }
-int q6k_set_gemm_min_n(int n) {
-    const int prev = q6k_gemm_min_n();
-    g_q6k_min_n.store(n < 0 ? -1 : (n < 9 ? 9 : n), std::memory_order_relaxed);     // -1: re-read the environment
+int GemmMinN::set(int n) {
+    const int prev = get();
+    v.store(n < 0 ? -1 : (n < 9 ? 9 : n), std::memory_order_relaxed);     // -1: re-read the environment
     return prev;
 }
-int q6k_auto_algo(int64_t K, int64_t, int64_t N) {
-    if (exact_mode()) return 4;
-    return (N >= q6k_gemm_min_n() || K > Q6K_GEMV_MAX_K) ? 5 : 1;
+
+// the measured crossovers.  Q6_K (tools/q6k_gemm_bench.py, profiles/q6k_gemm.json, lm_head shape): the
+// GEMM wins at every swept N from 9, the rule's floor.  Q8_0 (tools/q8_0_bench.py, profiles/q8_0_gemm.json, 4096 x
+// 4096): the tiled GEMV wins at N = 9 and 16 (16.2 / 22.7 us against the GEMM arm's flat 35 us, most of it the
+// per-call image), the GEMM from N = 32 (35.3 against 43.4 us).  Q5_K / Q4_K (tools/q45k_gemm_bench.py,
+// profiles/q45k_gemm.json; the LLaMA-7B layer shapes, weights from memory): the GEMM's time is flat in N up to 128,
+// so the tiled GEMV wins at N = 9 and ties at N = 16; from N = 32 the GEMM wins on every shape of both types (Q5_K
+// 4096 -> 4096: 52.5 against 99.6 us).  One threshold for the two: their crossovers do not differ.
+static GemmMinN g_q6k_min_n{"GGML_HIP_Q6K_GEMM_MIN_N", 9};
+static GemmMinN g_q8_0_min_n{"GGML_HIP_Q8_0_GEMM_MIN_N", 32};
+static GemmMinN g_q45k_min_n{"GGML_HIP_Q45K_GEMM_MIN_N", 32};
+
+// the K a type's GEMV takes: one token's q8_K image in the LDS for the k-quants (w2 of a 30B / 65B model has K =
+// 17920 / 22016), one token's q8_0 for Q8_0
+static bool gemv_takes_k_kquant(int64_t K) { return K <= 16384; }
+static bool gemv_takes_k_q8_0(int64_t K) { return ghip::gemv_q8_0w_max_tokens(K) >= 1; }
+
+static MulMatSig mul_mat_q6k_dev, mul_mat_q8_0_dev, mul_mat_q5k_dev, mul_mat_q4k_dev;
+
+static constexpr const char *ERR_K256 = "K must be a multiple of 256 (QK_K)";
+static constexpr const char *ERR_ALIGN_Q45K = "W and x must be 16-byte, y 4-byte aligned";
+static constexpr const char *ERR_GEMV_Q45K = "the Q5_K / Q4_K GEMV supports K <= 16384";
+static constexpr const char *ERR_DQ_Q45K = "w and the Q5_K / Q4_K rows must be 16-byte aligned";
+
+// Where the GEMV cannot take K, auto runs the GEMM on Q6_K and Q8_0 and the exact kernel, which has no K limit, on
+// Q5_K / Q4_K (so no shape the hook path accepts fails, and a long K computes what it did before their GEMM existed).
+// The Q5_K / Q4_K blocks are multiples of 16 bytes and their kernels read them as naturally aligned vectors.
+// fields, in WeightType's order: K granule, W alignment, M limit | GEMM algo, algo where the GEMV cannot take K, threshold,
+// the GEMV's K rule, run | texts: K granule, alignment, GEMV K | dequantizer: K granule, row alignment, text
+static const WeightType ROW_Q6_K = {
+    QK_K, 2, (int64_t)1 << 31,
+    5, 5, &g_q6k_min_n, gemv_takes_k_kquant, mul_mat_q6k_dev,
+    ERR_K256, "W must be 2-byte, x 16-byte, y 4-byte aligned", "the Q6_K GEMV supports K <= 16384",
+    QK_K, 2, "w must be 16-byte aligned, the Q6_K rows 2-byte aligned"};
+static const WeightType ROW_Q8_0 = {
+    64, 4, 1 << 30,
+    2, 2, &g_q8_0_min_n, gemv_takes_k_q8_0, mul_mat_q8_0_dev,
+    "K must be a multiple of 64 (ggml.c:3236 nb % 2 == 0)", "W must be 4-byte, x 16-byte, y 4-byte aligned",
+    "K too long for the Q8_0 GEMV",
+    QK, 2, "w must be 16-byte aligned, the Q8_0 rows 2-byte aligned"};
+static const WeightType ROW_Q5_K = {
+    QK_K, 16, (int64_t)1 << 31,
+    6, 4, &g_q45k_min_n, gemv_takes_k_kquant, mul_mat_q5k_dev,
+    ERR_K256, ERR_ALIGN_Q45K, ERR_GEMV_Q45K,
+    QK_K, 16, ERR_DQ_Q45K};
+static const WeightType ROW_Q4_K = {
+    QK_K, 16, (int64_t)1 << 31,
+    6, 4, &g_q45k_min_n, gemv_takes_k_kquant, mul_mat_q4k_dev,
+    ERR_K256, ERR_ALIGN_Q45K, ERR_GEMV_Q45K,
+    QK_K, 16, ERR_DQ_Q45K};
+
+const WeightType *weight_type(int type) {
+    switch (type) {
+        case gabi::TYPE_Q6_K: return &ROW_Q6_K;
+        case gabi::TYPE_Q8_0: return &ROW_Q8_0;
+        case gabi::TYPE_Q5_K: return &ROW_Q5_K;
+        case gabi::TYPE_Q4_K: return &ROW_Q4_K;
+        default: return nullptr;
+    }
 }
 
-int mul_mat_q6k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
-                    hipStream_t s) {
+int auto_algo(const WeightType &t, int64_t K, int64_t N) {
+    if (exact_mode()) return 4;
+    if (!t.gemv_takes_k(K)) return t.no_gemv_algo;
+    return N >= t.min_n->get() ? t.gemm_algo : 1;
+}
+
+// OK with N == 0 means there is nothing to run: the steps behind it are not checked then
+int check_operands(const WeightType &t, const void *w, int64_t K, int64_t M, const float *x, int64_t N, const float *y,
+                   int64_t ldy) {
     if (!w || !x || !y || K <= 0 || M <= 0 || N < 0) return fail(GGML_HIP_ERR_INVALID, "null pointer or bad shape");
-    if (K % QK_K != 0) return fail(GGML_HIP_ERR_INVALID, "K must be a multiple of 256 (QK_K)");
+    if (K % t.k_granule != 0) return fail(GGML_HIP_ERR_INVALID, t.err_k);
     if (N == 0) return GGML_HIP_OK;
     if (ldy < M) return fail(GGML_HIP_ERR_INVALID, "ldy < M");
-    if (!aligned(w, 2) || !aligned(x, 16) || !aligned(y, 4))
-        return fail(GGML_HIP_ERR_INVALID, "W must be 2-byte, x 16-byte, y 4-byte aligned");
-    if (M >= ((int64_t)1 << 31) || N * K >= ((int64_t)1 << 31))
+    if (!aligned(w, t.w_align) || !aligned(x, 16) || !aligned(y, 4)) return fail(GGML_HIP_ERR_INVALID, t.err_align);
+    if (M >= t.m_limit || N * K >= ((int64_t)1 << 31))
         return fail(GGML_HIP_ERR_UNSUPPORTED, "matrix too large for 32-bit indices; split rows or columns");
+    return GGML_HIP_OK;
+}
+
+// the workspaces of the k-quant arms.  Exact: x as q8_K blocks.  Q6_K GEMM: qs int8 [N][K] + d f32 [N][K / 256].
+// Q5_K / Q4_K GEMM: qs int8 [N][K] + dig int8 [N][K / 256][16] + d f32 [N][K / 256], 256 + 20 bytes per 256 elements
+// against the 288 of workspace_bytes(K, N) behind the same padding of qs.  None is more than workspace_bytes(K, N),
+// which ggml_hip_reserve_workspace reserves.
+static size_t workspace_bytes_q8k(int64_t K, int64_t N) { return (size_t)N * (size_t)(K / QK_K) * Q8KB; }
+static size_t kquant_planes_offset(int64_t K, int64_t N) { return (size_t)(N * K + 255) & ~(size_t)255; }
+static size_t workspace_bytes_q6k_gemm(int64_t K, int64_t N) {
+    return kquant_planes_offset(K, N) + (size_t)N * (size_t)(K / QK_K) * 4;
+}
+static size_t workspace_bytes_q45k_gemm(int64_t K, int64_t N) {
+    return kquant_planes_offset(K, N) + (size_t)N * (size_t)(K / QK_K) * 20;
+}
+
+static bool too_many_tiles(int64_t M, int64_t N) { return ((M + 63) / 64) * ((N + 63) / 64) >= ((int64_t)1 << 31); }
+static constexpr const char *ERR_TILES = "too many tiles for one grid; split rows or columns";
+
+// the exact arm of the k-quants: the q8_K quantizer into the stream's workspace; *ws = the blocks
+static int quantize_q8k_ws(int id, const float *x, int64_t K, int64_t N, hipStream_t s, void **ws) {
+    const int wrc = stream_workspace(id, s, workspace_bytes_q8k(K, N), ws);
+    if (wrc != GGML_HIP_OK) return wrc;
+    HIP_RET(ghip::quantize_q8_K(x, K, N, *ws, s));
+    return GGML_HIP_OK;
+}
+
+// Q6_K (q6_k.hip, q6_k_gemm.hip): algo 5 = the q8_K values of x as planes in the workspace + k_gemm_q6_K
+static int mul_mat_q6k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                           hipStream_t s) {
+    const int rc = check_operands(ROW_Q6_K, w, K, M, x, N, y, ldy);
+    if (rc != GGML_HIP_OK || N == 0) return rc;
     const int id = current_device();
-    if (algo == 0) algo = q6k_auto_algo(K, M, N);
+    if (algo == 0) algo = auto_algo(ROW_Q6_K, K, N);
     if (algo == 1) {
-        if (K > Q6K_GEMV_MAX_K) return fail(GGML_HIP_ERR_UNSUPPORTED, "the Q6_K GEMV supports K <= 16384");
+        if (!ROW_Q6_K.gemv_takes_k(K)) return fail(GGML_HIP_ERR_UNSUPPORTED, ROW_Q6_K.err_gemv_k);
         HIP_RET(ghip::gemv_q6_K(w, K, M, x, N, y, ldy, g_dev[id].info, s));
         return GGML_HIP_OK;
     }
     if (algo != 4 && algo != 5) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1, 4 or 5");
     void *ws = nullptr;
     if (algo == 5) {
-        if (((M + 63) / 64) * ((N + 63) / 64) >= ((int64_t)1 << 31))
-            return fail(GGML_HIP_ERR_UNSUPPORTED, "too many tiles for one grid; split rows or columns");
+        if (too_many_tiles(M, N)) return fail(GGML_HIP_ERR_UNSUPPORTED, ERR_TILES);
         const int wrc = stream_workspace(id, s, workspace_bytes_q6k_gemm(K, N), &ws);
         if (wrc != GGML_HIP_OK) return wrc;
-        float *xd = (float *)((char *)ws + ((size_t)(N * K + 255) & ~(size_t)255));
+        float *xd = (float *)((char *)ws + kquant_planes_offset(K, N));
         HIP_RET(ghip::quantize_q8_K_planes(x, K, N, ws, xd, s));
         HIP_RET(ghip::gemm_q6_K(w, K, M, ws, xd, N, y, ldy, s));
         return GGML_HIP_OK;
     }
-    const int wrc = stream_workspace(id, s, workspace_bytes_q8k(K, N), &ws);
+    const int wrc = quantize_q8k_ws(id, x, K, N, s, &ws);
     if (wrc != GGML_HIP_OK) return wrc;
-    HIP_RET(ghip::quantize_q8_K(x, K, N, ws, s));
     HIP_RET(ghip::mm_exact_q6_K(w, K, M, ws, N, y, ldy, s));
     return GGML_HIP_OK;
 }
 
-// The Q8_0-weight mul_mat (q8_0_w.hip).  Decode: the fused GEMV (column tiles above gemv_q8_0w_max_tokens(K)).
-// Prefill: the weight's k_gemm8 image built per call into the stream's workspace (k_prep8_w_q8_0; the way GEMM
-// version 9 treats an unregistered q4_0 weight; ggml_hip_reserve_workspace_mm budgets its 34 B per 32 weights),
-// then gemm8_prep_x + gemm8_run unchanged.  Exact mode: the SoA q8_0 quantizer into the workspace and the exact
-// kernel.  Auto takes the GEMM from N >= q8_0_gemm_min_n() (tools/q8_0_bench.py, DESIGN §4b;
-// GGML_HIP_Q8_0_GEMM_MIN_N / ggml_hip_debug_set_q8_0_gemm_min_n, never below 9) and wherever the GEMV cannot
-// run (one token's q8_0 larger than the LDS).
-// the sweep (profiles/q8_0_gemm.json, 4096 x 4096): the tiled GEMV wins at N = 9 and 16 (16.2 / 22.7 us against
-// the GEMM arm's flat 35 us, most of it the per-call image), the GEMM from N = 32 (35.3 against 43.4 us)
-static constexpr int Q8_0_GEMM_MIN_N = 32;
-std::atomic<int> g_q8_0_min_n{-1};
-int q8_0_gemm_min_n() {
-    int v = g_q8_0_min_n.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *e = getenv("GGML_HIP_Q8_0_GEMM_MIN_N");
-        int want = e ? atoi(e) : Q8_0_GEMM_MIN_N, expect = -1;
-        if (want < 9) want = 9;
-        g_q8_0_min_n.compare_exchange_strong(expect, want);
-        v = g_q8_0_min_n.load(std::memory_order_relaxed);
-    }
-    return v;
-}
-int q8_0_set_gemm_min_n(int n) {
-    const int prev = q8_0_gemm_min_n();
-    g_q8_0_min_n.store(n < 0 ? -1 : (n < 9 ? 9 : n), std::memory_order_relaxed);    // -1: re-read the environment
-    return prev;
-}
-int q8_0_auto_algo(int64_t K, int64_t, int64_t N) {
-    if (exact_mode()) return 4;
-    return (N >= q8_0_gemm_min_n() || ghip::gemv_q8_0w_max_tokens(K) < 1) ? 2 : 1;
-}
-
-int mul_mat_q8_0_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
-                     hipStream_t s) {
-    if (!w || !x || !y || K <= 0 || M <= 0 || N < 0) return fail(GGML_HIP_ERR_INVALID, "null pointer or bad shape");
-    if (K % 64 != 0) return fail(GGML_HIP_ERR_INVALID, "K must be a multiple of 64 (ggml.c:3236 nb % 2 == 0)");
-    if (N == 0) return GGML_HIP_OK;
-    if (ldy < M) return fail(GGML_HIP_ERR_INVALID, "ldy < M");
-    if (!aligned(w, 4) || !aligned(x, 16) || !aligned(y, 4))
-        return fail(GGML_HIP_ERR_INVALID, "W must be 4-byte, x 16-byte, y 4-byte aligned");
-    if (M >= (1 << 30) || N * K >= ((int64_t)1 << 31))
-        return fail(GGML_HIP_ERR_UNSUPPORTED, "matrix too large for 32-bit indices; split rows or columns");
+// Q8_0 weights (q8_0_w.hip): algo 2 = the weight's k_gemm8 image built per call into the workspace (k_prep8_w_q8_0;
+// the way GEMM version 9 treats an unregistered q4_0 weight; ggml_hip_reserve_workspace_mm budgets its 34 B per 32
+// weights), then gemm8_prep_x + gemm8_run unchanged; algo 4 = the SoA q8_0 quantizer + the exact kernel
+static int mul_mat_q8_0_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                            hipStream_t s) {
+    const int rc = check_operands(ROW_Q8_0, w, K, M, x, N, y, ldy);
+    if (rc != GGML_HIP_OK || N == 0) return rc;
     const int id = current_device();
-    if (algo == 0) algo = q8_0_auto_algo(K, M, N);
+    if (algo == 0) algo = auto_algo(ROW_Q8_0, K, N);
     if (algo == 1) {
-        if (ghip::gemv_q8_0w_max_tokens(K) < 1) return fail(GGML_HIP_ERR_UNSUPPORTED, "K too long for the Q8_0 GEMV");
+        if (!ROW_Q8_0.gemv_takes_k(K)) return fail(GGML_HIP_ERR_UNSUPPORTED, ROW_Q8_0.err_gemv_k);
         HIP_RET(ghip::gemv_q8_0w(w, K, M, x, N, y, ldy, g_dev[id].info, s));
         return GGML_HIP_OK;
     }
@@ -437,91 +483,45 @@ int mul_mat_q8_0_dev(const void *w, int64_t K, int64_t M, const float *x, int64_
     return GGML_HIP_OK;
 }
 
-// The Q5_K / Q4_K mul_mat (q45_k.hip, q45_k_gemm.hip; type = gabi::TYPE_Q5_K or TYPE_Q4_K).  Decode: the fused
-// GEMV (column tiles of 8 above N = 8).  Prefill: the q8_K values of x as planes in the stream's workspace and the
-// int8-MFMA GEMM k_gemm_q45_K (algo 6; 5 stays invalid for these types), whose y is bit for bit the GEMV's (the
-// same exact integer superblock sums, the same fp32 step per superblock in the same order), so the switch between
-// the two never changes a result.  Exact mode: the q8_K quantizer into the workspace and the exact kernel, which
-// auto also takes for K > 16384, where the GEMV cannot run (so no shape the hook path accepts fails here, and a
-// long K computes what it did before the GEMM existed).  Auto takes the GEMM from N >= q45k_gemm_min_n()
-// (tools/q45k_gemm_bench.py; GGML_HIP_Q45K_GEMM_MIN_N / ggml_hip_debug_set_q45k_gemm_min_n, never
-// below 9).  The blocks are multiples of 16 bytes and the kernels read them as naturally aligned vectors, so W
-// must be 16-byte aligned.
-// qs int8 [N][K] + dig int8 [N][K / 256][16] + d f32 [N][K / 256]: 256 + 20 bytes per 256 elements against the 288
-// of workspace_bytes(K, N) behind the same padding of qs, so never more than ggml_hip_reserve_workspace reserves
-static size_t q45k_dig_offset(int64_t K, int64_t N) { return (size_t)(N * K + 255) & ~(size_t)255; }
-size_t workspace_bytes_q45k_gemm(int64_t K, int64_t N) {
-    return q45k_dig_offset(K, N) + (size_t)N * (size_t)(K / QK_K) * 20;
-}
-
-// the sweep (profiles/q45k_gemm.json; 4096 -> 4096, 4096 -> 11008, 11008 -> 4096, weights from memory): the GEMM's
-// time is flat in N up to 128 (Q5_K: 51 / 52 / 129 us at N = 9), so the tiled GEMV wins at N = 9 on 4096 -> 4096 and
-// 11008 -> 4096 (33 and 86 us) and ties at N = 16 on Q5_K 4096 -> 4096 (50.8 against 51.6 us); from N = 32 the GEMM
-// wins on every shape of both types (Q5_K 4096 -> 4096: 52.5 against 99.6 us).  One threshold: the types' crossovers
-// do not differ.
-static constexpr int Q45K_GEMM_MIN_N = 32;
-static constexpr int Q45K_GEMV_MAX_K = 16384;
-std::atomic<int> g_q45k_min_n{-1};
-int q45k_gemm_min_n() {
-    int v = g_q45k_min_n.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *e = getenv("GGML_HIP_Q45K_GEMM_MIN_N");
-        int want = e ? atoi(e) : Q45K_GEMM_MIN_N, expect = -1;
-        if (want < 9) want = 9;
-        g_q45k_min_n.compare_exchange_strong(expect, want);
-        v = g_q45k_min_n.load(std::memory_order_relaxed);
-    }
-    return v;
-}
-int q45k_set_gemm_min_n(int n) {
-    const int prev = q45k_gemm_min_n();
-    g_q45k_min_n.store(n < 0 ? -1 : (n < 9 ? 9 : n), std::memory_order_relaxed);    // -1: re-read the environment
-    return prev;
-}
-int q45k_auto_algo(int64_t K, int64_t, int64_t N) {
-    if (exact_mode() || K > Q45K_GEMV_MAX_K) return 4;
-    return N >= q45k_gemm_min_n() ? 6 : 1;
-}
-
-int mul_mat_q45k_dev(int type, const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
-                     int algo, hipStream_t s) {
-    if (type != gabi::TYPE_Q5_K && type != gabi::TYPE_Q4_K) return fail(GGML_HIP_ERR_INVALID, "type must be Q5_K or Q4_K");
-    const bool qh = type == gabi::TYPE_Q5_K;
-    if (!w || !x || !y || K <= 0 || M <= 0 || N < 0) return fail(GGML_HIP_ERR_INVALID, "null pointer or bad shape");
-    if (K % QK_K != 0) return fail(GGML_HIP_ERR_INVALID, "K must be a multiple of 256 (QK_K)");
+// Q5_K (qh) / Q4_K (q45_k.hip, q45_k_gemm.hip): algo 6 = the q8_K values of x and their sub-block sums' digits as
+// planes in the workspace + k_gemm_q45_K (5 stays invalid for these types).  An algo the types reject is refused
+// before anything else, an empty call included.
+static int mul_mat_q45k_dev(bool qh, const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
+                            int algo, hipStream_t s) {
     if (algo != 0 && algo != 1 && algo != 4 && algo != 6) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1, 4 or 6");
-    if (N == 0) return GGML_HIP_OK;
-    if (ldy < M) return fail(GGML_HIP_ERR_INVALID, "ldy < M");
-    if (!aligned(w, 16) || !aligned(x, 16) || !aligned(y, 4))
-        return fail(GGML_HIP_ERR_INVALID, "W and x must be 16-byte, y 4-byte aligned");
-    if (M >= ((int64_t)1 << 31) || N * K >= ((int64_t)1 << 31))
-        return fail(GGML_HIP_ERR_UNSUPPORTED, "matrix too large for 32-bit indices; split rows or columns");
+    const WeightType &t = ROW_Q5_K;                      // (the two rows differ in the run function only)
+    const int rc = check_operands(t, w, K, M, x, N, y, ldy);
+    if (rc != GGML_HIP_OK || N == 0) return rc;
     const int id = current_device();
-    // auto never fails on K: above the GEMV's limit (one token's q8_K image larger than the LDS; w2 of a 30B / 65B
-    // model has K = 17920 / 22016) it takes the exact kernel, which has no K limit
-    if (algo == 0) algo = q45k_auto_algo(K, M, N);
+    if (algo == 0) algo = auto_algo(t, K, N);
     if (algo == 1) {
-        if (K > Q45K_GEMV_MAX_K) return fail(GGML_HIP_ERR_UNSUPPORTED, "the Q5_K / Q4_K GEMV supports K <= 16384");
+        if (!t.gemv_takes_k(K)) return fail(GGML_HIP_ERR_UNSUPPORTED, t.err_gemv_k);
         HIP_RET(ghip::gemv_q45_K(qh, w, K, M, x, N, y, ldy, g_dev[id].info, s));
         return GGML_HIP_OK;
     }
     void *ws = nullptr;
     if (algo == 6) {
-        if (((M + 63) / 64) * ((N + 63) / 64) >= ((int64_t)1 << 31))
-            return fail(GGML_HIP_ERR_UNSUPPORTED, "too many tiles for one grid; split rows or columns");
+        if (too_many_tiles(M, N)) return fail(GGML_HIP_ERR_UNSUPPORTED, ERR_TILES);
         const int wrc = stream_workspace(id, s, workspace_bytes_q45k_gemm(K, N), &ws);
         if (wrc != GGML_HIP_OK) return wrc;
-        void *dig = (char *)ws + q45k_dig_offset(K, N);
+        void *dig = (char *)ws + kquant_planes_offset(K, N);
         float *xd = (float *)((char *)dig + (size_t)N * (size_t)(K / QK_K) * 16);
         HIP_RET(ghip::quantize_q8_K_digit_planes(x, K, N, ws, xd, dig, s));
         HIP_RET(ghip::gemm_q45_K(qh, w, K, M, ws, xd, dig, N, y, ldy, g_dev[id].info, s));
         return GGML_HIP_OK;
     }
-    const int wrc = stream_workspace(id, s, workspace_bytes_q8k(K, N), &ws);
+    const int wrc = quantize_q8k_ws(id, x, K, N, s, &ws);
     if (wrc != GGML_HIP_OK) return wrc;
-    HIP_RET(ghip::quantize_q8_K(x, K, N, ws, s));
     HIP_RET(ghip::mm_exact_q45_K(qh, w, K, M, ws, N, y, ldy, s));
     return GGML_HIP_OK;
+}
+static int mul_mat_q5k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                           hipStream_t s) {
+    return mul_mat_q45k_dev(true, w, K, M, x, N, y, ldy, algo, s);
+}
+static int mul_mat_q4k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                           hipStream_t s) {
+    return mul_mat_q45k_dev(false, w, K, M, x, N, y, ldy, algo, s);
 }
 
 // Sibling matrices (one x) that all take k_gemm9 on a registered fp6 image: ONE launch over their
@@ -590,38 +590,16 @@ bool supported_mul_mat(const tensor *src0, const tensor *src1, const tensor *dst
            src0->ne[3] == src1->ne[3] && is_contiguous(src0) && is_contiguous(src1) && is_contiguous(dst);
 }
 
-// contiguous Q6_K x F32 -> F32 (a k-quants model's output.weight); kept apart from supported_mul_mat, which
-// gates everything q4_0-only: the q4_0 kernels, weight images, sibling groups, chains and the engine
-bool supported_mul_mat_q6k(const tensor *src0, const tensor *src1, const tensor *dst) {
-    return src0 && src1 && dst && src0->type == gabi::TYPE_Q6_K && src1->type == gabi::TYPE_F32 &&
-           dst->type == gabi::TYPE_F32 && src0->ne[0] > 0 && src0->ne[0] % QK_K == 0 && src0->ne[0] == src1->ne[0] &&
-           dst->ne[0] == src0->ne[1] && dst->ne[1] == src1->ne[1] && src0->ne[2] == src1->ne[2] &&
-           src0->ne[3] == src1->ne[3] && is_contiguous(src0) && is_contiguous(src1) && is_contiguous(dst);
-}
-
-// contiguous Q8_0 x F32 -> F32 (the layer matrices of a "mostly Q8_0" file); a predicate of its own for the same
-// reason: no Q8_0 node reaches a q4_0 or Q6_K kernel, a weight image, a sibling group or a chain
-bool supported_mul_mat_q8_0(const tensor *src0, const tensor *src1, const tensor *dst) {
-    return src0 && src1 && dst && src0->type == gabi::TYPE_Q8_0 && src1->type == gabi::TYPE_F32 &&
-           dst->type == gabi::TYPE_F32 && src0->ne[0] > 0 && src0->ne[0] % 64 == 0 && src0->ne[0] == src1->ne[0] &&
-           dst->ne[0] == src0->ne[1] && dst->ne[1] == src1->ne[1] && src0->ne[2] == src1->ne[2] &&
-           src0->ne[3] == src1->ne[3] && is_contiguous(src0) && is_contiguous(src1) && is_contiguous(dst);
-}
-
-// contiguous Q5_K / Q4_K x F32 -> F32 (the layer matrices of a "mostly Q5_K" / "mostly Q4_K" file); predicates of
-// their own for the same reason.  They look at the operands only: the hook path asks q4k_enabled() beside
-// supported_mul_mat_q4k wherever it takes a Q4_K tensor (ggml-hip-tensor.cpp)
-static bool supported_mul_mat_k256(int type, const tensor *src0, const tensor *src1, const tensor *dst) {
-    return src0 && src1 && dst && src0->type == type && src1->type == gabi::TYPE_F32 &&
-           dst->type == gabi::TYPE_F32 && src0->ne[0] > 0 && src0->ne[0] % QK_K == 0 && src0->ne[0] == src1->ne[0] &&
-           dst->ne[0] == src0->ne[1] && dst->ne[1] == src1->ne[1] && src0->ne[2] == src1->ne[2] &&
-           src0->ne[3] == src1->ne[3] && is_contiguous(src0) && is_contiguous(src1) && is_contiguous(dst);
-}
-bool supported_mul_mat_q5k(const tensor *src0, const tensor *src1, const tensor *dst) {
-    return supported_mul_mat_k256(gabi::TYPE_Q5_K, src0, src1, dst);
-}
-bool supported_mul_mat_q4k(const tensor *src0, const tensor *src1, const tensor *dst) {
-    return supported_mul_mat_k256(gabi::TYPE_Q4_K, src0, src1, dst);
+// contiguous <type> x F32 -> F32 for a type with a row in weight_type()'s table.  Kept apart from supported_mul_mat,
+// which gates everything q4_0-only (the q4_0 kernels, weight images, sibling groups, chains and the engine), so
+// that no node of another type reaches those.  It looks at the operands only, not at the Q4_K switch.
+bool supported_mul_mat_type(int type, const tensor *src0, const tensor *src1, const tensor *dst) {
+    const WeightType *t = weight_type(type);
+    return t && src0 && src1 && dst && src0->type == type && src1->type == gabi::TYPE_F32 &&
+           dst->type == gabi::TYPE_F32 && src0->ne[0] > 0 && src0->ne[0] % t->k_granule == 0 &&
+           src0->ne[0] == src1->ne[0] && dst->ne[0] == src0->ne[1] && dst->ne[1] == src1->ne[1] &&
+           src0->ne[2] == src1->ne[2] && src0->ne[3] == src1->ne[3] && is_contiguous(src0) && is_contiguous(src1) &&
+           is_contiguous(dst);
 }
 
 // Q4_K on the hook path is opt-in: GGML_HIP_Q4_K=1 or ggml_hip_debug_set_q4_K
@@ -640,6 +618,20 @@ int q4k_set_enabled(int on) {
     const int prev = q4k_enabled() ? 1 : 0;
     g_q4k.store(on ? 1 : 0, std::memory_order_relaxed);
     return prev;
+}
+
+// The hook path's two questions about a weight type.  With the Q4_K switch off every entry point treats a
+// host-resident Q4_K tensor as a type no device op reads; a Q4_K weight that transform_tensor uploaded while the
+// switch was on keeps being served after it is turned off: its data is on the device, so ggml's CPU op could not
+// read it.
+bool hook_takes_type(int type) {
+    return type == gabi::TYPE_Q4_0 || (weight_type(type) && (type != gabi::TYPE_Q4_K || q4k_enabled()));
+}
+int hook_weight_type(const tensor *src0, const tensor *src1, const tensor *dst) {
+    if (supported_mul_mat(src0, src1, dst)) return gabi::TYPE_Q4_0;
+    if (!src0 || !supported_mul_mat_type(src0->type, src0, src1, dst)) return gabi::TYPE_COUNT;
+    if (src0->type == gabi::TYPE_Q4_K && !q4k_enabled() && !(on_device(src0) && src0->extra)) return gabi::TYPE_COUNT;
+    return src0->type;
 }
 
 [[noreturn]] void op_abort(const tensor *t, const char *why) {

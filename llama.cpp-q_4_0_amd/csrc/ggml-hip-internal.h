@@ -156,32 +156,42 @@ int mul_mat_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, 
                 hipStream_t s, unsigned *xq = nullptr);
 int mul_mat_group_g9(int n, const void *const *w, const int64_t *M, int64_t K, const float *x, int64_t N,
                      float *const *y, hipStream_t s);
-// the Q6_K mul_mat: algo 0 auto (q6k_auto_algo), 1 GEMV (column tiles of 8), 4 exact, 5 int8-MFMA GEMM
-size_t workspace_bytes_q8k(int64_t K, int64_t N);
-size_t workspace_bytes_q6k_gemm(int64_t K, int64_t N);
-int q6k_auto_algo(int64_t K, int64_t M, int64_t N);     // what algo 0 runs now: 1, 4 or 5 (no device needed)
-int q6k_gemm_min_n();
-int q6k_set_gemm_min_n(int n);                          // -1: the environment value or the default; returns the previous
-int mul_mat_q6k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
-                    hipStream_t s);
-// the Q8_0-weight mul_mat: algo 0 auto (q8_0_auto_algo), 1 GEMV (column tiles), 2 per-call int8 image + k_gemm8,
-// 4 exact
-int q8_0_auto_algo(int64_t K, int64_t M, int64_t N);    // what algo 0 runs now: 1, 2 or 4 (no device needed)
-int q8_0_gemm_min_n();
-int q8_0_set_gemm_min_n(int n);                         // -1: the environment value or the default; returns the previous
-int mul_mat_q8_0_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
-                     hipStream_t s);
-// the Q5_K / Q4_K mul_mat (type = gabi::TYPE_Q5_K or TYPE_Q4_K): algo 0 auto (q45k_auto_algo), 1 GEMV (column tiles
-// of 8), 4 exact, 6 int8-MFMA GEMM; w 16-byte aligned
-size_t workspace_bytes_q45k_gemm(int64_t K, int64_t N);
-int q45k_auto_algo(int64_t K, int64_t M, int64_t N);    // what algo 0 runs now: 1, 4 or 6 (no device needed)
-int q45k_gemm_min_n();
-int q45k_set_gemm_min_n(int n);                         // -1: the environment value or the default; returns the previous
-int mul_mat_q45k_dev(int type, const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
-                     int algo, hipStream_t s);
+// ---- the weight types beside Q4_0: one row each in weight_type()'s table (ggml-hip-core.cpp)
+// a type's GEMM threshold: the smallest N at which auto takes the GEMM; never below 9
+struct GemmMinN {
+    const char *env;                  // read on first use
+    int dflt;                         // the measured crossover
+    std::atomic<int> v{-1};
+    int get();
+    int set(int n);                   // -1: the environment value or the default; returns the previous
+};
+using MulMatSig = int(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                      hipStream_t s);
+struct WeightType {
+    int k_granule;                    // K is a multiple of this
+    size_t w_align;                   // of W, in bytes
+    int64_t m_limit;                  // M is below this
+    int gemm_algo, no_gemv_algo;      // what auto runs from the threshold / where the GEMV cannot take K
+    GemmMinN *min_n;
+    bool (*gemv_takes_k)(int64_t K);
+    MulMatSig *run;                   // the mul_mat on device pointers: algo 0 auto, 1 GEMV, 4 exact, gemm_algo
+    const char *err_k, *err_align, *err_gemv_k;
+    // the dequantizer's arguments (ggml-hip-api.cpp)
+    int dq_granule;
+    size_t dq_align;
+    const char *err_dq_align;
+};
+const WeightType *weight_type(int type);                // null: the type has no row
+int auto_algo(const WeightType &t, int64_t K, int64_t N);   // what algo 0 runs now (no device needed)
+int check_operands(const WeightType &t, const void *w, int64_t K, int64_t M, const float *x, int64_t N, const float *y,
+                   int64_t ldy);
 // the hook path takes Q4_K tensors only with this switch on (GGML_HIP_Q4_K=1 / ggml_hip_debug_set_q4_K; default off)
 bool q4k_enabled();
 int q4k_set_enabled(int on);                            // returns the previous value (0 / 1)
+// the hook path (ggml-hip-tensor.cpp): is `type` a device weight type now / the weight type whose mul_mat this
+// node is, gabi::TYPE_COUNT for none
+bool hook_takes_type(int type);
+int hook_weight_type(const tensor *src0, const tensor *src1, const tensor *dst);
 // true when ggml_hip_mul_mat_q4_0_multi runs these n siblings at N tokens as ONE k_gemm9 launch on registered
 // fp6 images (mul_mat_group_g9 for n > 1, mul_mat_dev's image GEMM for n = 1); img[i] = the images
 bool g9_images(int n, const void *const *w, const int64_t *M, int64_t K, int64_t N, const void **img);
@@ -191,10 +201,7 @@ bool is_contiguous(const tensor *t);
 bool on_device(const tensor *t);
 void split_range(int64_t nrows, int id, int64_t *lo, int64_t *hi);
 bool supported_mul_mat(const tensor *src0, const tensor *src1, const tensor *dst);
-bool supported_mul_mat_q6k(const tensor *src0, const tensor *src1, const tensor *dst);
-bool supported_mul_mat_q8_0(const tensor *src0, const tensor *src1, const tensor *dst);
-bool supported_mul_mat_q5k(const tensor *src0, const tensor *src1, const tensor *dst);
-bool supported_mul_mat_q4k(const tensor *src0, const tensor *src1, const tensor *dst);   // operands only, not the switch
+bool supported_mul_mat_type(int type, const tensor *src0, const tensor *src1, const tensor *dst);   // operands only
 [[noreturn]] void op_abort(const tensor *t, const char *why);
 inline bool same_shape(const tensor *a, const tensor *b) {
     return a->ne[0] == b->ne[0] && a->ne[1] == b->ne[1] && a->ne[2] == b->ne[2] && a->ne[3] == b->ne[3];

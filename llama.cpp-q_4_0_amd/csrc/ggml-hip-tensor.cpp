@@ -98,20 +98,6 @@ namespace ghh {
 std::mutex g_host_copy_mu;
 std::unordered_map<const void *, void *> g_host_copies;
 
-// The k-quant layer types of q45_k.hip / q45_k_gemm.hip as the hook path takes them (always with algo 0: the GEMV,
-// from N >= q45k_gemm_min_n() the GEMM, bitwise the same y): Q5_K always, Q4_K only with its switch on
-// (q4k_enabled(): GGML_HIP_Q4_K=1 / ggml_hip_debug_set_q4_K).  With the switch off every entry
-// point below treats a host-resident Q4_K tensor as a type no device op reads.  A Q4_K weight that
-// transform_tensor uploaded while the switch was on keeps being served after it is turned off: its data is on
-// the device, so ggml's CPU op could not read it.
-static bool hook_type_q45k(int type) {
-    return type == gabi::TYPE_Q5_K || (type == gabi::TYPE_Q4_K && q4k_enabled());
-}
-static bool hook_mul_mat_q45k(const tensor *src0, const tensor *src1, const tensor *dst) {
-    return supported_mul_mat_q5k(src0, src1, dst) ||
-           (supported_mul_mat_q4k(src0, src1, dst) && (q4k_enabled() || (on_device(src0) && src0->extra)));
-}
-
 }  // namespace ghh
 
 extern "C" {
@@ -130,25 +116,20 @@ void ggml_hip_set_tensor_split(const float *tensor_split) {
 }
 
 bool ggml_hip_can_mul_mat(const struct ggml_tensor *src0_, const struct ggml_tensor *src1_, struct ggml_tensor *dst_) {
-    // ggml-cuda.cu:2595-2610, restricted to the q4_0 path this backend implements, the Q6_K output.weight and
-    // Q8_0, Q5_K and (behind its switch) Q4_K weights
+    // ggml-cuda.cu:2595-2610, restricted to the weight types this backend implements (hook_weight_type)
     const tensor *src0 = (const tensor *)src0_, *src1 = (const tensor *)src1_, *dst = (const tensor *)dst_;
-    if (!supported_mul_mat(src0, src1, dst) && !supported_mul_mat_q6k(src0, src1, dst) &&
-        !supported_mul_mat_q8_0(src0, src1, dst) && !hook_mul_mat_q45k(src0, src1, dst))
-        return false;
+    if (hook_weight_type(src0, src1, dst) == gabi::TYPE_COUNT) return false;
     // no device: decline, so ggml.c plans and runs its own CPU mul_mat (the reference would route
     // the op here regardless and fail inside ggml_cuda_mul_mat)
     ensure_init();
     if (g_device_count == 0) return false;
     if (dst->ne[0] >= 32 && dst->ne[1] >= 32 && src1->ne[0] >= 32) return true;
-    // Decode (N < 32) of a host-resident Q4_0 (or Q6_K, Q8_0, Q5_K, Q4_K) weight: the reference declines it (each call would
+    // Decode (N < 32) of a host-resident quantized weight: the reference declines it (each call would
     // re-upload the weight, ggml-cuda.cu:2496-2502), so the arch/ frontends, which never offload,
     // decode on the CPU.  Here the weight-residency cache keeps the weight on the device after its
     // first use, so a weight of at least GGML_HIP_DECODE_MIN_WEIGHTS elements (default 2^19: one
     // LLaMA/Falcon projection is 2^24) is taken at any N; smaller ones stay on ggml's CPU op.
-    return (src0->type == gabi::TYPE_Q4_0 || src0->type == gabi::TYPE_Q6_K || src0->type == gabi::TYPE_Q8_0 ||
-            hook_type_q45k(src0->type)) &&
-           wcache_enabled() &&
+    return hook_takes_type(src0->type) && wcache_enabled() &&
            (uint64_t)src0->ne[0] * (uint64_t)src0->ne[1] >= (uint64_t)decode_min_weights();
 }
 
@@ -166,17 +147,14 @@ void ggml_hip_mul_mat(const struct ggml_tensor *src0, const struct ggml_tensor *
 
 namespace ghh {
 
-// the q4_0 (or Q6_K, Q8_0, Q5_K, Q4_K) mul_mat of one node; leaves a pending fusion chain alone (try_fuse checked that the two
-// touch disjoint buffers)
+// the quantized mul_mat of one node; leaves a pending fusion chain alone (try_fuse checked that the two touch
+// disjoint buffers)
 void mul_mat_node(const tensor *src0, const tensor *src1, tensor *dst) {
     // ggml_cuda_mul_mat -> ggml_cuda_op (ggml-cuda.cu:2671-2690, 2286-2567)
-    // dispatch by weight type: a Q6_K, Q8_0, Q5_K or Q4_K node never reaches a q4_0 kernel or image, nor one
-    // another's
-    const gabi::type wtype = supported_mul_mat(src0, src1, dst)        ? gabi::TYPE_Q4_0
-                             : supported_mul_mat_q6k(src0, src1, dst)  ? gabi::TYPE_Q6_K
-                             : supported_mul_mat_q8_0(src0, src1, dst) ? gabi::TYPE_Q8_0
-                             : hook_mul_mat_q45k(src0, src1, dst)      ? (gabi::type)src0->type
-                                                                       : gabi::TYPE_COUNT;
+    // dispatch by weight type, classified once: a node of a type with a row runs that row's mul_mat and never
+    // reaches a q4_0 kernel or image, nor another type's kernels
+    const int wtype = hook_weight_type(src0, src1, dst);
+    const WeightType *row = weight_type(wtype);          // null: Q4_0
     if (wtype == gabi::TYPE_COUNT) {
         fprintf(stderr, "ggml_hip_mul_mat: unsupported operands (need contiguous Q4_0 or Q8_0 x F32 -> F32, K %% 64 == 0, "
                         "or Q6_K, Q5_K (Q4_K with GGML_HIP_Q4_K=1) x F32 -> F32, K %% 256 == 0)\n");
@@ -200,7 +178,7 @@ void mul_mat_node(const tensor *src0, const tensor *src1, tensor *dst) {
     const bool src0_dev = on_device(src0);
     const bool src1_dev = src1->backend == gabi::BACKEND_GPU;
     const bool dst_dev = dst->backend == gabi::BACKEND_GPU;
-    const size_t wrow = src0->nb[1];                   // 18 K / 32 (Q4_0), 34 K / 32 (Q8_0), 210 / 176 / 144 K / 256 (Q6_K / Q5_K / Q4_K)
+    const size_t wrow = src0->nb[1];                   // bytes of a weight row (18 K / 32 for Q4_0)
     const int saved = current_device();
     const int main_id = g_main_device;
     const uint64_t call_id = wcache_next_call_id();
@@ -289,14 +267,7 @@ void mul_mat_node(const tensor *src0, const tensor *src1, tensor *dst) {
                 y = (float *)tmp_alloc(id, (size_t)N * rows * 4);
                 ldy = rows;
             }
-            int rc;
-            switch (wtype) {
-                case gabi::TYPE_Q6_K: rc = mul_mat_q6k_dev(w, K, rows, x, N, y, ldy, 0, s); break;
-                case gabi::TYPE_Q8_0: rc = mul_mat_q8_0_dev(w, K, rows, x, N, y, ldy, 0, s); break;
-                case gabi::TYPE_Q5_K:
-                case gabi::TYPE_Q4_K: rc = mul_mat_q45k_dev(wtype, w, K, rows, x, N, y, ldy, 0, s); break;
-                default: rc = mul_mat_dev(w, K, rows, x, N, y, ldy, 0, s); break;
-            }
+            const int rc = row ? row->run(w, K, rows, x, N, y, ldy, 0, s) : mul_mat_dev(w, K, rows, x, N, y, ldy, 0, s);
             if (rc != GGML_HIP_OK) {
                 fprintf(stderr, "ggml_hip_mul_mat: %s\n", g_last_error.c_str());
                 abort();
@@ -377,8 +348,7 @@ void ggml_hip_transform_tensor(void *data, struct ggml_tensor *tensor_) {
     ensure_init();
     flush_deferred();
     tensor *t = (tensor *)tensor_;
-    if ((t->type != gabi::TYPE_Q4_0 && t->type != gabi::TYPE_Q6_K && t->type != gabi::TYPE_Q8_0 &&
-         !hook_type_q45k(t->type) && t->type != gabi::TYPE_F32 && t->type != gabi::TYPE_F16) || g_device_count == 0) {
+    if ((!hook_takes_type(t->type) && t->type != gabi::TYPE_F32 && t->type != gabi::TYPE_F16) || g_device_count == 0) {
         // A type no device op reads: ggml.c computes the ops that read it on the CPU and asserts
         // CPU operands there (ggml.c:15650), so the tensor stays a CPU tensor, on a host copy this
         // backend owns (the loader may free `data` after the call, llama.cpp:680-683).
@@ -398,9 +368,8 @@ void ggml_hip_transform_tensor(void *data, struct ggml_tensor *tensor_) {
         t->extra = nullptr;
         return;
     }
-    if (t->type != gabi::TYPE_Q4_0 && t->type != gabi::TYPE_Q6_K && t->type != gabi::TYPE_Q8_0 &&
-        !hook_type_q45k(t->type) && t->backend == gabi::BACKEND_GPU_SPLIT)
-        t->backend = gabi::BACKEND_GPU;   // only the Q4_0 / Q6_K / Q8_0 / Q5_K / Q4_K mul_mats read row-split operands
+    if (!hook_takes_type(t->type) && t->backend == gabi::BACKEND_GPU_SPLIT)
+        t->backend = gabi::BACKEND_GPU;   // only the quantized mul_mats read row-split operands
     const int64_t nrows = gabi::nrows(t);
     const size_t nb1 = t->nb[1];
     auto *extra = new ggml_tensor_extra_gpu;
@@ -520,9 +489,8 @@ void ggml_hip_free_scratch(void) {
 bool ggml_hip_compute_forward(struct ggml_compute_params *params_, struct ggml_tensor *tensor_) {
     // ggml-cuda.cu:2933-3021: a node is taken when any operand is device resident (MUL_MAT also when
     // can_mul_mat holds for host operands); only ith == 0 in COMPUTE executes (the other threads
-    // spin in ggml.c:17285-17287).  Q4_0 mul_mat -> the q4_0 kernels, Q6_K mul_mat -> q6_k.hip, Q8_0 mul_mat ->
-    // q8_0_w.hip, Q5_K (and, switched on, Q4_K) mul_mat -> q45_k.hip; F16 mul_mat (attention on the KV cache) and the other ops of a LLaMA layer -> ggml_ops.hip; views
-    // are free.
+    // spin in ggml.c:17285-17287).  A quantized mul_mat -> its weight type's kernels (hook_weight_type); F16
+    // mul_mat (attention on the KV cache) and the other ops of a LLaMA layer -> ggml_ops.hip; views are free.
     const gabi::compute_params *params = (const gabi::compute_params *)params_;
     tensor *t = (tensor *)tensor_;
     // a host write into cached weights (LoRA apply) invalidates their device copies; INIT runs once per
@@ -540,9 +508,7 @@ bool ggml_hip_compute_forward(struct ggml_compute_params *params_, struct ggml_t
                 f16_mul_mat = true;
                 break;
             }
-            if (!supported_mul_mat(t->src0, t->src1, t) && !supported_mul_mat_q6k(t->src0, t->src1, t) &&
-                !supported_mul_mat_q8_0(t->src0, t->src1, t) && !hook_mul_mat_q45k(t->src0, t->src1, t))
-                return false;
+            if (hook_weight_type(t->src0, t->src1, t) == gabi::TYPE_COUNT) return false;
             ensure_init();
             if (g_device_count == 0) return false;
             if (!any_on_device && !ggml_hip_can_mul_mat((const ggml_tensor *)t->src0, (const ggml_tensor *)t->src1,

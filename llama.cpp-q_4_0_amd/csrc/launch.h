@@ -100,4 +100,64 @@ inline void launch_k(void (*k)(P...), dim3 grid, dim3 block, size_t lds, hipStre
     rec_kernel((const void *)k, grid, block, lds, s, (int)sizeof...(P), ptrs, sizes, aligns);
 }
 
+// ---- launch scaffolding shared by the kernel files' host halves
+
+// hipFuncAttributeMaxDynamicSharedMemorySize of Kernel raised to `bytes`, once per device: every instantiation
+// has its own flag word, one bit per device (16 max), thread-safe
+template <auto Kernel>
+inline hipError_t raise_dynamic_lds(int bytes) {
+    static std::atomic<uint32_t> done{0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 15) dev = 0;
+    if (done.load(std::memory_order_acquire) & (1u << dev)) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) done.fetch_or(1u << dev, std::memory_order_acq_rel);
+    return e;
+}
+
+// the 1-D launch of a quantizer or dequantizer: blocks of 256 threads, `per_block` of the `items` each; nothing
+// to do is success
+template <typename... P, typename... A>
+inline hipError_t launch_1d(void (*k)(P...), int64_t items, int per_block, hipStream_t s, A &&...a) {
+    if (items == 0) return hipSuccess;
+    (void)hipGetLastError();  // report only this launch's error
+    launch_k(k, dim3((unsigned)((items + per_block - 1) / per_block)), dim3(256), 0, s, std::forward<A>(a)...);
+    return hipGetLastError();
+}
+
+// a GEMV's run-time token tile nt in 1 .. 8 as a template argument: f(std::integral_constant<int, nt>)
+template <class F>
+inline hipError_t with_token_tile(int nt, F &&f) {
+    switch (nt) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+    }
+    return hipErrorInvalidValue;
+}
+
+// any N through a GEMV of at most `tile` tokens per launch: f(n0, nt) on the column tiles in order, up to the
+// first error (each tile is exactly the call on those columns)
+template <class F>
+inline hipError_t for_column_tiles(int64_t N, int tile, F &&f) {
+    for (int64_t n0 = 0; n0 < N; n0 += tile) {
+        const hipError_t e = f(n0, (int)(N - n0 < tile ? N - n0 : tile));
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// an exact kernel's columns on grid.y, at most 65535 per launch: launch(n0, nn) issues columns [n0, n0 + nn)
+template <class F>
+inline hipError_t launch_column_chunks(int64_t N, F &&launch) {
+    (void)hipGetLastError();  // report only these launches' error
+    for (int64_t n0 = 0; n0 < N; n0 += 65535) launch(n0, (unsigned)(N - n0 < 65535 ? N - n0 : 65535));
+    return hipGetLastError();
+}
+
 }  // namespace ghip

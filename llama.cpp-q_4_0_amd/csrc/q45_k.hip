@@ -25,8 +25,6 @@
 // so y does not depend on the grid, the row mapping or the token tile, and x -> 2x doubles every term exactly.
 #include "q45_k_device.h"
 
-#include <atomic>
-
 namespace ghip {
 
 // ---------------------------------------------------------------------------------------------
@@ -56,11 +54,7 @@ __global__ __launch_bounds__(256) void k_dequantize_q45_K(const uint8_t *__restr
 template <bool QH>
 static hipError_t dequantize_q45_K_t(const void *wq, int64_t K, int64_t M, float *w, hipStream_t s) {
     const int64_t nquads = M * K / 4;
-    if (nquads == 0) return hipSuccess;
-    (void)hipGetLastError();  // report only this launch's error
-    launch_k(k_dequantize_q45_K<QH>, dim3((unsigned)((nquads + 255) / 256)), dim3(256), 0, s, (const uint8_t *)wq, nquads,
-             w);
-    return hipGetLastError();
+    return launch_1d(k_dequantize_q45_K<QH>, nquads, 256, s, (const uint8_t *)wq, nquads, w);
 }
 
 hipError_t dequantize_q45_K(bool qh, const void *wq, int64_t K, int64_t M, float *w, hipStream_t s) {
@@ -221,15 +215,9 @@ template <bool QH, int NT>
 static hipError_t launch_gemv45(const uint8_t *W, int nb, int M, const float *x, float *y, int64_t ldy, int num_cus,
                                 hipStream_t s) {
     const size_t lds = (size_t)NT * (size_t)nb * GEMV45_LDS_PER_BLOCK;
-    static std::atomic<uint32_t> attr{0};            // one bit per device (16 max), thread-safe
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 15) dev = 0;
-    if (!(attr.load(std::memory_order_acquire) & (1u << dev))) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_gemv_q45_K<QH, NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           NT * (GEMV45_MAX_K / QK_K) * GEMV45_LDS_PER_BLOCK);
-        if (e != hipSuccess) return e;
-        attr.fetch_or(1u << dev, std::memory_order_acq_rel);
-    }
+    // (the limit for GEMV45_MAX_K, not this launch's lds: it is set once)
+    const hipError_t e = raise_dynamic_lds<k_gemv_q45_K<QH, NT>>(NT * (GEMV45_MAX_K / QK_K) * GEMV45_LDS_PER_BLOCK);
+    if (e != hipSuccess) return e;
     const int per = GEMV45_THREADS / 64;
     const int64_t want = ((int64_t)M + per - 1) / per;
     // one workgroup per CU; rows beyond the grid are strided (y does not depend on this choice)
@@ -246,25 +234,12 @@ static hipError_t gemv_q45_K_t(const void *W, int64_t K, int64_t M, const float 
                                const DeviceInfo &dev, hipStream_t s) {
     if (K <= 0 || K % QK_K || K > GEMV45_MAX_K || M < 1 || M >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
     const int nb = (int)(K / QK_K);
-    const uint8_t *w = (const uint8_t *)W;
-    for (int64_t n0 = 0; n0 < N; n0 += 8) {
-        const int nt = (int)(N - n0 < 8 ? N - n0 : 8);
-        const float *xt = x + n0 * K;
-        float *yt = y + n0 * ldy;
-        hipError_t e = hipErrorInvalidValue;
-        switch (nt) {
-            case 1: e = launch_gemv45<QH, 1>(w, nb, (int)M, xt, yt, ldy, dev.num_cus, s); break;
-            case 2: e = launch_gemv45<QH, 2>(w, nb, (int)M, xt, yt, ldy, dev.num_cus, s); break;
-            case 3: e = launch_gemv45<QH, 3>(w, nb, (int)M, xt, yt, ldy, dev.num_cus, s); break;
-            case 4: e = launch_gemv45<QH, 4>(w, nb, (int)M, xt, yt, ldy, dev.num_cus, s); break;
-            case 5: e = launch_gemv45<QH, 5>(w, nb, (int)M, xt, yt, ldy, dev.num_cus, s); break;
-            case 6: e = launch_gemv45<QH, 6>(w, nb, (int)M, xt, yt, ldy, dev.num_cus, s); break;
-            case 7: e = launch_gemv45<QH, 7>(w, nb, (int)M, xt, yt, ldy, dev.num_cus, s); break;
-            case 8: e = launch_gemv45<QH, 8>(w, nb, (int)M, xt, yt, ldy, dev.num_cus, s); break;
-        }
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return for_column_tiles(N, 8, [&](int64_t n0, int nt) {
+        return with_token_tile(nt, [&](auto NT) {
+            return launch_gemv45<QH, decltype(NT)::value>((const uint8_t *)W, nb, (int)M, x + n0 * K, y + n0 * ldy, ldy,
+                                                          dev.num_cus, s);
+        });
+    });
 }
 
 hipError_t gemv_q45_K(bool qh, const void *W, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
@@ -354,14 +329,11 @@ template <bool QH>
 static hipError_t mm_exact_q45_K_t(const void *W, int64_t K, int64_t M, const void *xq8k, int64_t N, float *y,
                                    int64_t ldy, hipStream_t s) {
     if (K <= 0 || K % QK_K || M < 1 || M >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-    (void)hipGetLastError();  // report only this launch's error
-    for (int64_t n0 = 0; n0 < N; n0 += 65535) {       // grid.y limit
-        const int64_t nn = N - n0 < 65535 ? N - n0 : 65535;
-        launch_k(k_mm_exact_q45_K<QH>, dim3((unsigned)((M + EX45_ROWS - 1) / EX45_ROWS), (unsigned)nn), dim3(EX45_ROWS * 8),
-                 0, s, (const uint8_t *)W, (int)(K / QK_K), (int)M, (const uint8_t *)xq8k + n0 * (K / QK_K) * Q8KB,
-                 y + n0 * ldy, ldy);
-    }
-    return hipGetLastError();
+    return launch_column_chunks(N, [&](int64_t n0, unsigned nn) {
+        launch_k(k_mm_exact_q45_K<QH>, dim3((unsigned)((M + EX45_ROWS - 1) / EX45_ROWS), nn), dim3(EX45_ROWS * 8), 0, s,
+                 (const uint8_t *)W, (int)(K / QK_K), (int)M, (const uint8_t *)xq8k + n0 * (K / QK_K) * Q8KB, y + n0 * ldy,
+                 ldy);
+    });
 }
 
 hipError_t mm_exact_q45_K(bool qh, const void *W, int64_t K, int64_t M, const void *xq8k, int64_t N, float *y, int64_t ldy,

@@ -47,8 +47,6 @@
 // superblock's global loads are issued before the current one's MFMAs.
 #include "q45_k_device.h"
 
-#include <atomic>
-
 namespace ghip {
 
 static constexpr int G45_BM = 64;                      // rows per workgroup
@@ -77,11 +75,7 @@ __global__ __launch_bounds__(256) void k_quantize_q8_K_digit_planes(const float 
 hipError_t quantize_q8_K_digit_planes(const float *x, int64_t K, int64_t N, void *qs, float *xd, void *dig,
                                       hipStream_t s) {
     const int64_t nblocks = N * (K / QK_K);
-    if (nblocks == 0) return hipSuccess;
-    (void)hipGetLastError();  // report only this launch's error
-    launch_k(k_quantize_q8_K_digit_planes, dim3((unsigned)((nblocks + 3) / 4)), dim3(256), 0, s, x, nblocks, (uint32_t *)qs,
-             xd, (int8_t *)dig);
-    return hipGetLastError();
+    return launch_1d(k_quantize_q8_K_digit_planes, nblocks, 4, s, x, nblocks, (uint32_t *)qs, xd, (int8_t *)dig);
 }
 
 // four 4- or 5-bit values (one per byte) and their sub-block's scale (<= 63) -> the int8 digits of w' = sc q =
@@ -272,15 +266,7 @@ static hipError_t launch_gemm45(const uint8_t *W, int nb, int M, const uint8_t *
                                 int N, float *y, int64_t ldy, hipStream_t s) {
     constexpr int BN = 32 * WN * TN;
     constexpr size_t lds = (size_t)(2 * G45_BM + BN) * G45_LD + (size_t)(G45_BM + 2 * BN) * 8 + (size_t)(2 * G45_BM + BN) * 4;
-    static std::atomic<uint32_t> attr{0};            // one bit per device (16 max), thread-safe
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 15) dev = 0;
-    if (!(attr.load(std::memory_order_acquire) & (1u << dev))) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_gemm_q45_K<QH, WN, TN>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr.fetch_or(1u << dev, std::memory_order_acq_rel);
-    }
+    if (const hipError_t e = raise_dynamic_lds<k_gemm_q45_K<QH, WN, TN>>((int)lds); e != hipSuccess) return e;
     const int64_t ntm = ((int64_t)M + G45_BM - 1) / G45_BM, ntn = ((int64_t)N + BN - 1) / BN;
     if (ntm * ntn >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
     (void)hipGetLastError();  // report only this launch's error

@@ -824,14 +824,7 @@ int engine_stamps(EnginePlan *p, uint64_t *out, int64_t n) {
 }
 
 hipError_t engine_launch(EnginePlan *p, hipStream_t s) {
-    static std::atomic<uint32_t> attr{0};          // one bit per device (16 max)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 15) dev = 0;
-    if (!(attr.load(std::memory_order_acquire) & (1u << dev))) {
-        const hipError_t e = hipFuncSetAttribute((const void *)k_engine_q4_0, hipFuncAttributeMaxDynamicSharedMemorySize, ENG_LDS);
-        if (e != hipSuccess) return e;
-        attr.fetch_or(1u << dev, std::memory_order_acq_rel);
-    }
+    if (const hipError_t e = raise_dynamic_lds<k_engine_q4_0>(ENG_LDS); e != hipSuccess) return e;
     EngArgs a;
     a.tasks = p->d_tasks;
     a.units = p->d_units;

@@ -2,8 +2,6 @@
 // Shared device helpers and the HBM layouts: q4_0_device.h / q4_0_kernels.h.
 #include "q4_0_device.h"
 
-#include <atomic>
-
 namespace ghip {
 
 // ---------------------------------------------------------------------------------------------
@@ -256,15 +254,7 @@ static hipError_t launch_exact(const ExMats &m, int n, int64_t K, const int8_t *
     const int nb = (int)(K / QK);
     const int64_t rowbytes = (int64_t)nb * Q4B;
     const int lds = ExLayout<NC, EXC, SLOTS>::S * ExLayout<NC, EXC, SLOTS>::SLOT;
-    static std::atomic<uint32_t> attr{0};            // one bit per device (16 max), thread-safe
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 15) dev = 0;
-    if (!(attr.load(std::memory_order_acquire) & (1u << dev))) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_mm_exact_q4_0<NC, EXC, SLOTS>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        attr.fetch_or(1u << dev, std::memory_order_acq_rel);
-    }
+    if (const hipError_t e = raise_dynamic_lds<k_mm_exact_q4_0<NC, EXC, SLOTS>>(lds); e != hipSuccess) return e;
     dim3 grid((unsigned)m.wg_begin[n], (unsigned)((N + NC - 1) / NC));
     (void)hipGetLastError();  // report only this launch's error
     launch_k(k_mm_exact_q4_0<NC, EXC, SLOTS>, grid, dim3(EX_THREADS), lds, s, m, rowbytes, nb, xqs, xd, (int)N, (int)K);

@@ -41,23 +41,14 @@ __global__ __launch_bounds__(256) void k_quantize_q8_0(const float *__restrict__
 
 hipError_t quantize_q8_0_aos(const float *x, int64_t K, int64_t N, void *xq8, hipStream_t s) {
     const int64_t total8 = N * (K / QK) * 8;
-    if (total8 == 0) return hipSuccess;
-    const int64_t grid = (total8 + 255) / 256;
-    (void)hipGetLastError();  // report only this launch's error
-    launch_k(k_quantize_q8_0<true>, dim3((unsigned)grid), dim3(256), 0, s, x, K, total8,
-                       (uint8_t *)xq8, (int8_t *)nullptr, (float *)nullptr, (uint16_t *)nullptr, N);
-    return hipGetLastError();
+    return launch_1d(k_quantize_q8_0<true>, total8, 256, s, x, K, total8, (uint8_t *)xq8, (int8_t *)nullptr, (float *)nullptr,
+                     (uint16_t *)nullptr, N);
 }
 
 hipError_t quantize_q8_0_soa(const float *x, int64_t K, int64_t N, int8_t *qs, float *d, hipStream_t s,
                              uint16_t *d16) {
     const int64_t total8 = N * (K / QK) * 8;
-    if (total8 == 0) return hipSuccess;
-    const int64_t grid = (total8 + 255) / 256;
-    (void)hipGetLastError();  // report only this launch's error
-    launch_k(k_quantize_q8_0<false>, dim3((unsigned)grid), dim3(256), 0, s, x, K, total8,
-                       (uint8_t *)nullptr, qs, d, d16, N);
-    return hipGetLastError();
+    return launch_1d(k_quantize_q8_0<false>, total8, 256, s, x, K, total8, (uint8_t *)nullptr, qs, d, d16, N);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -101,11 +92,7 @@ __global__ __launch_bounds__(256) void k_quantize_q4_0(const float *__restrict__
 
 hipError_t quantize_q4_0(const float *w, int64_t K, int64_t M, void *wq, hipStream_t s) {
     const int64_t nblocks = M * (K / QK);
-    if (nblocks == 0) return hipSuccess;
-    (void)hipGetLastError();  // report only this launch's error
-    launch_k(k_quantize_q4_0, dim3((unsigned)((nblocks + 255) / 256)), dim3(256), 0, s, w, nblocks,
-                       (uint8_t *)wq);
-    return hipGetLastError();
+    return launch_1d(k_quantize_q4_0, nblocks, 256, s, w, nblocks, (uint8_t *)wq);
 }
 
 // A4
@@ -124,11 +111,7 @@ __global__ __launch_bounds__(256) void k_dequantize_q4_0(const uint8_t *__restri
 
 hipError_t dequantize_q4_0(const void *wq, int64_t K, int64_t M, float *w, hipStream_t s) {
     const int64_t nblocks = M * (K / QK);
-    if (nblocks == 0) return hipSuccess;
-    (void)hipGetLastError();  // report only this launch's error
-    launch_k(k_dequantize_q4_0, dim3((unsigned)((nblocks * 16 + 255) / 256)), dim3(256), 0, s,
-                       (const uint8_t *)wq, nblocks, w);
-    return hipGetLastError();
+    return launch_1d(k_dequantize_q4_0, nblocks * 16, 256, s, (const uint8_t *)wq, nblocks, w);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -183,12 +166,7 @@ __global__ __launch_bounds__(256) void k_fill_gaussian(float *__restrict__ dst, 
 }
 
 hipError_t fill_gaussian(float *dst, int64_t n, uint64_t seed, float mean, float stdv, hipStream_t s) {
-    const int64_t pairs = (n + 1) / 2;
-    if (pairs == 0) return hipSuccess;
-    (void)hipGetLastError();  // report only this launch's error
-    launch_k(k_fill_gaussian, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, dst, n, seed, mean,
-                       stdv);
-    return hipGetLastError();
+    return launch_1d(k_fill_gaussian, (n + 1) / 2, 256, s, dst, n, seed, mean, stdv);
 }
 
 }  // namespace ghip

@@ -28,8 +28,6 @@
 // per stage in a single LDS buffer; the next superblock's global loads are issued before the current one's MFMAs.
 #include "q6_k_device.h"
 
-#include <atomic>
-
 namespace ghip {
 
 typedef short s16x2 __attribute__((ext_vector_type(2)));
@@ -52,10 +50,7 @@ __global__ __launch_bounds__(256) void k_quantize_q8_K_planes(const float *__res
 
 hipError_t quantize_q8_K_planes(const float *x, int64_t K, int64_t N, void *qs, float *xd, hipStream_t s) {
     const int64_t nblocks = N * (K / QK_K);
-    if (nblocks == 0) return hipSuccess;
-    (void)hipGetLastError();  // report only this launch's error
-    launch_k(k_quantize_q8_K_planes, dim3((unsigned)((nblocks + 3) / 4)), dim3(256), 0, s, x, nblocks, (uint32_t *)qs, xd);
-    return hipGetLastError();
+    return launch_1d(k_quantize_q8_K_planes, nblocks, 4, s, x, nblocks, (uint32_t *)qs, xd);
 }
 
 // four 6-bit values (one per byte) and their scale -> the int8 digits of w' = sc (q - 32) = 128 hi + lo, packed
@@ -237,15 +232,7 @@ static hipError_t launch_gemm6(const uint8_t *W, int nb, int M, const uint8_t *x
                                int64_t ldy, hipStream_t s) {
     constexpr int BN = 32 * WN * TN;
     constexpr size_t lds = (size_t)(2 * G6_BM + BN) * G6_LD + (size_t)(G6_BM + BN) * 4;
-    static std::atomic<uint32_t> attr{0};            // one bit per device (16 max), thread-safe
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 15) dev = 0;
-    if (!(attr.load(std::memory_order_acquire) & (1u << dev))) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_gemm_q6_K<WN, TN>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) return e;
-        attr.fetch_or(1u << dev, std::memory_order_acq_rel);
-    }
+    if (const hipError_t e = raise_dynamic_lds<k_gemm_q6_K<WN, TN>>((int)lds); e != hipSuccess) return e;
     const int64_t ntm = ((int64_t)M + G6_BM - 1) / G6_BM, ntn = ((int64_t)N + BN - 1) / BN;
     if (ntm * ntn >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
     (void)hipGetLastError();  // report only this launch's error

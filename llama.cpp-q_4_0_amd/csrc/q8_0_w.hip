@@ -40,10 +40,7 @@ __global__ __launch_bounds__(256) void k_dequantize_q8_0(const uint8_t *__restri
 
 hipError_t dequantize_q8_0(const void *wq, int64_t K, int64_t M, float *w, hipStream_t s) {
     const int64_t nquads = M * K / 4;
-    if (nquads == 0) return hipSuccess;
-    (void)hipGetLastError();  // report only this launch's error
-    launch_k(k_dequantize_q8_0, dim3((unsigned)((nquads + 255) / 256)), dim3(256), 0, s, (const uint8_t *)wq, nquads, w);
-    return hipGetLastError();
+    return launch_1d(k_dequantize_q8_0, nquads, 256, s, (const uint8_t *)wq, nquads, w);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -283,25 +280,12 @@ hipError_t gemv_q8_0w(const void *W, int64_t K, int64_t M, const float *x, int64
     const int tile = gemv_q8_0w_max_tokens(K);
     if (K <= 0 || K % 64 || tile < 1 || M < 1 || M >= ((int64_t)1 << 30)) return hipErrorInvalidValue;
     const int nb = (int)(K / QK);
-    const uint8_t *w = (const uint8_t *)W;
-    for (int64_t n0 = 0; n0 < N; n0 += tile) {
-        const int nt = (int)(N - n0 < tile ? N - n0 : tile);
-        const float *xt = x + n0 * K;
-        float *yt = y + n0 * ldy;
-        hipError_t e = hipErrorInvalidValue;
-        switch (nt) {
-            case 1: e = launch_gemv8w_d<1>(w, nb, M, xt, yt, ldy, dev.num_cus, s); break;
-            case 2: e = launch_gemv8w_d<2>(w, nb, M, xt, yt, ldy, dev.num_cus, s); break;
-            case 3: e = launch_gemv8w_d<3>(w, nb, M, xt, yt, ldy, dev.num_cus, s); break;
-            case 4: e = launch_gemv8w_d<4>(w, nb, M, xt, yt, ldy, dev.num_cus, s); break;
-            case 5: e = launch_gemv8w_d<5>(w, nb, M, xt, yt, ldy, dev.num_cus, s); break;
-            case 6: e = launch_gemv8w_d<6>(w, nb, M, xt, yt, ldy, dev.num_cus, s); break;
-            case 7: e = launch_gemv8w_d<7>(w, nb, M, xt, yt, ldy, dev.num_cus, s); break;
-            case 8: e = launch_gemv8w_d<8>(w, nb, M, xt, yt, ldy, dev.num_cus, s); break;
-        }
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return for_column_tiles(N, tile, [&](int64_t n0, int nt) {
+        return with_token_tile(nt, [&](auto NT) {
+            return launch_gemv8w_d<decltype(NT)::value>((const uint8_t *)W, nb, M, x + n0 * K, y + n0 * ldy, ldy, dev.num_cus,
+                                                        s);
+        });
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -346,13 +330,10 @@ __global__ __launch_bounds__(EX8_ROWS * 8) void k_mm_exact_q8_0w(const uint8_t *
 hipError_t mm_exact_q8_0w(const void *W, int64_t K, int64_t M, const int8_t *xqs, const float *xd, int64_t N, float *y,
                           int64_t ldy, hipStream_t s) {
     if (K <= 0 || K % 64 || M < 1 || M >= ((int64_t)1 << 30)) return hipErrorInvalidValue;
-    (void)hipGetLastError();  // report only this launch's error
-    for (int64_t n0 = 0; n0 < N; n0 += 65535) {       // grid.y limit
-        const int64_t nn = N - n0 < 65535 ? N - n0 : 65535;
-        launch_k(k_mm_exact_q8_0w, dim3((unsigned)((M + EX8_ROWS - 1) / EX8_ROWS), (unsigned)nn), dim3(EX8_ROWS * 8), 0, s,
+    return launch_column_chunks(N, [&](int64_t n0, unsigned nn) {
+        launch_k(k_mm_exact_q8_0w, dim3((unsigned)((M + EX8_ROWS - 1) / EX8_ROWS), nn), dim3(EX8_ROWS * 8), 0, s,
                  (const uint8_t *)W, (int)(K / QK), (int)M, xqs + n0 * K, xd + n0 * (K / QK), y + n0 * ldy, ldy);
-    }
-    return hipGetLastError();
+    });
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -272,11 +272,16 @@ def dequantize_q6_K(wq_dev, K, M, w_dev, stream=None):
     check(load().ggml_hip_dequantize_q6_K(_ptr(wq_dev), K, M, _ptr(w_dev), stream), "dequantize_q6_K")
 
 
+def _mul_mat_typed(name, w_dev, K, M, x_dev, N, y_dev, algo, ldy, stream, w_off, x_off, y_off):
+    """The shared body of mul_mat_q6_K / _q8_0 / _q5_K / _q4_K: ggml_hip_<name> on buffers or raw pointers."""
+    check(getattr(load(), "ggml_hip_" + name)(_ptr(w_dev) + w_off, K, M, _ptr(x_dev) + x_off, N, _ptr(y_dev) + y_off,
+                                              M if ldy is None else ldy, algo, stream), name)
+
+
 def mul_mat_q6_K(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_off=0, x_off=0, y_off=0):
     """Q6_K rows (210 * K / 256 bytes each) x f32 [N][K] -> f32 y[n * ldy + m]; algo 0 auto (exact mode: 4; N at or
     above the GEMM threshold, or K > 16384: 5; else 1), 1 GEMV, 4 exact, 5 int8-MFMA GEMM (bitwise algo 1)."""
-    check(load().ggml_hip_mul_mat_q6_K(_ptr(w_dev) + w_off, K, M, _ptr(x_dev) + x_off, N, _ptr(y_dev) + y_off,
-                                       M if ldy is None else ldy, algo, stream), "mul_mat_q6_K")
+    _mul_mat_typed("mul_mat_q6_K", w_dev, K, M, x_dev, N, y_dev, algo, ldy, stream, w_off, x_off, y_off)
 
 
 def dequantize_q8_0(wq_dev, K, M, w_dev, stream=None):
@@ -286,8 +291,7 @@ def dequantize_q8_0(wq_dev, K, M, w_dev, stream=None):
 def mul_mat_q8_0(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_off=0, x_off=0, y_off=0):
     """Q8_0 weight rows (34 * K / 32 bytes each) x f32 [N][K] -> f32 y[n * ldy + m]; algo 0 auto (exact mode: 4; N
     below the GEMM threshold: 1; else 2), 1 GEMV, 2 per-call int8 image + int8-MFMA GEMM, 4 exact."""
-    check(load().ggml_hip_mul_mat_q8_0(_ptr(w_dev) + w_off, K, M, _ptr(x_dev) + x_off, N, _ptr(y_dev) + y_off,
-                                       M if ldy is None else ldy, algo, stream), "mul_mat_q8_0")
+    _mul_mat_typed("mul_mat_q8_0", w_dev, K, M, x_dev, N, y_dev, algo, ldy, stream, w_off, x_off, y_off)
 
 
 def dequantize_q5_K(wq_dev, K, M, w_dev, stream=None):
@@ -302,15 +306,13 @@ def mul_mat_q5_K(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_
     """Q5_K rows (176 * K / 256 bytes each, 16-byte aligned) x f32 [N][K] -> f32 y[n * ldy + m]; algo 0 auto (exact
     mode or K > 16384: 4; N below the GEMM threshold: 1; else 6), 1 GEMV (column tiles of 8, K <= 16384), 4 exact,
     6 int8-MFMA GEMM (bitwise algo 1)."""
-    check(load().ggml_hip_mul_mat_q5_K(_ptr(w_dev) + w_off, K, M, _ptr(x_dev) + x_off, N, _ptr(y_dev) + y_off,
-                                       M if ldy is None else ldy, algo, stream), "mul_mat_q5_K")
+    _mul_mat_typed("mul_mat_q5_K", w_dev, K, M, x_dev, N, y_dev, algo, ldy, stream, w_off, x_off, y_off)
 
 
 def mul_mat_q4_K(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_off=0, x_off=0, y_off=0):
     """Q4_K rows (144 * K / 256 bytes each, 16-byte aligned) x f32 [N][K] -> f32 y[n * ldy + m]; algos as
     mul_mat_q5_K.  Always available here; the tensor hook path takes Q4_K only with ggml_hip_debug_set_q4_K(1)."""
-    check(load().ggml_hip_mul_mat_q4_K(_ptr(w_dev) + w_off, K, M, _ptr(x_dev) + x_off, N, _ptr(y_dev) + y_off,
-                                       M if ldy is None else ldy, algo, stream), "mul_mat_q4_K")
+    _mul_mat_typed("mul_mat_q4_K", w_dev, K, M, x_dev, N, y_dev, algo, ldy, stream, w_off, x_off, y_off)
 
 
 def debug_q45k_auto_algo(gtype, K, M, N):

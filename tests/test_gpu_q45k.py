@@ -246,6 +246,15 @@ def test_status_codes(exact_off, variant):
         assert mm(b.ptr + off, 256, 4, b.ptr, 1, b.ptr, 4, 0, None) == ggml_hip.ERR_INVALID
         assert dq(b.ptr + off, 256, 1, b.ptr, None) == ggml_hip.ERR_INVALID
     assert mm(b.ptr, 256, 4, b.ptr, 0, b.ptr, 4, 0, None) == ggml_hip.OK                   # N = 0
+    for algo in (2, 3, 5, -1):
+        assert mm(b.ptr, 256, 4, b.ptr, 0, b.ptr, 4, algo, None) == ggml_hip.ERR_INVALID   # the algo check comes first
+    assert mm(None, 256, 4, b.ptr, 1, b.ptr, 4, 0, None) == ggml_hip.ERR_INVALID
+    assert mm(b.ptr, 256, 4, None, 1, b.ptr, 4, 0, None) == ggml_hip.ERR_INVALID
+    assert mm(b.ptr, 256, 4, b.ptr, 1, None, 4, 0, None) == ggml_hip.ERR_INVALID
+    assert mm(b.ptr, 256, 4, b.ptr + 4, 1, b.ptr, 4, 0, None) == ggml_hip.ERR_INVALID      # x not 16-byte aligned
+    assert mm(b.ptr, 256, 4, b.ptr, 1, b.ptr + 2, 4, 0, None) == ggml_hip.ERR_INVALID      # y not 4-byte aligned
+    assert mm(b.ptr, 16640, 4, b.ptr, 0, b.ptr, 4, 1, None) == ggml_hip.OK                 # K past the GEMV, nothing to run
+    assert mm(b.ptr, 16640, 4, b.ptr, 1, b.ptr, 4, 1, None) == ggml_hip.ERR_UNSUPPORTED    # (refused before any launch)
 
 
 # ---- hook path --------------------------------------------------------------------------------------------

@@ -351,6 +351,17 @@ def test_status_codes(exact_off):
     assert L.ggml_hip_mul_mat_q6_K(b.ptr, 256, 4, b.ptr, 1, b.ptr, 3, 0, None) == ggml_hip.ERR_INVALID    # ldy < M
     assert L.ggml_hip_mul_mat_q6_K(b.ptr, 256, 4, b.ptr, 1, b.ptr, 4, 2, None) == ggml_hip.ERR_INVALID    # algo
     assert L.ggml_hip_mul_mat_q6_K(b.ptr, 256, 4, b.ptr, 0, b.ptr, 4, 0, None) == ggml_hip.OK             # N = 0
+    mm = L.ggml_hip_mul_mat_q6_K
+    for algo in (2, 3, 6, -1):
+        assert mm(b.ptr, 256, 4, b.ptr, 0, b.ptr, 4, algo, None) == ggml_hip.OK          # N = 0 returns before the algo check
+    assert mm(None, 256, 4, b.ptr, 1, b.ptr, 4, 0, None) == ggml_hip.ERR_INVALID
+    assert mm(b.ptr, 256, 4, None, 1, b.ptr, 4, 0, None) == ggml_hip.ERR_INVALID
+    assert mm(b.ptr, 256, 4, b.ptr, 1, None, 4, 0, None) == ggml_hip.ERR_INVALID
+    assert mm(b.ptr, 256, 4, b.ptr + 4, 1, b.ptr, 4, 0, None) == ggml_hip.ERR_INVALID    # x not 16-byte aligned
+    assert mm(b.ptr, 256, 4, b.ptr, 1, b.ptr + 2, 4, 0, None) == ggml_hip.ERR_INVALID    # y not 4-byte aligned
+    assert mm(b.ptr + 1, 256, 4, b.ptr, 1, b.ptr, 4, 0, None) == ggml_hip.ERR_INVALID    # W not 2-byte aligned
+    assert mm(b.ptr, 16640, 4, b.ptr, 0, b.ptr, 4, 1, None) == ggml_hip.OK               # K past the GEMV, nothing to run
+    assert mm(b.ptr, 16640, 4, b.ptr, 1, b.ptr, 4, 1, None) == ggml_hip.ERR_UNSUPPORTED  # (refused before any launch)
 
 
 # ---- 13. launch fusion ------------------------------------------------------------------------------------

@@ -319,6 +319,16 @@ def test_status_codes(exact_off):
         assert mm(b.ptr, 64, 4, b.ptr, 1, b.ptr, 4, algo, None) == ggml_hip.ERR_INVALID  # algo
     assert mm(None, 64, 4, b.ptr, 1, b.ptr, 4, 0, None) == ggml_hip.ERR_INVALID
     assert mm(b.ptr, 64, 4, b.ptr, 0, b.ptr, 4, 0, None) == ggml_hip.OK                  # N = 0
+    for algo in (3, 5, 6, -1):
+        assert mm(b.ptr, 64, 4, b.ptr, 0, b.ptr, 4, algo, None) == ggml_hip.OK           # N = 0 returns before the algo check
+    assert mm(b.ptr, 64, 4, None, 1, b.ptr, 4, 0, None) == ggml_hip.ERR_INVALID
+    assert mm(b.ptr, 64, 4, b.ptr, 1, None, 4, 0, None) == ggml_hip.ERR_INVALID
+    assert mm(b.ptr, 64, 4, b.ptr + 4, 1, b.ptr, 4, 0, None) == ggml_hip.ERR_INVALID     # x not 16-byte aligned
+    assert mm(b.ptr, 64, 4, b.ptr, 1, b.ptr + 2, 4, 0, None) == ggml_hip.ERR_INVALID     # y not 4-byte aligned
+    assert mm(b.ptr + 2, 64, 4, b.ptr, 1, b.ptr, 4, 0, None) == ggml_hip.ERR_INVALID     # W not 4-byte aligned
+    # K = 58304: 1822 blocks, one token's q8_0 (36 bytes per block) is past the GEMV's 64 KiB of LDS
+    assert mm(b.ptr, 58304, 4, b.ptr, 0, b.ptr, 4, 1, None) == ggml_hip.OK               # nothing to run
+    assert mm(b.ptr, 58304, 4, b.ptr, 1, b.ptr, 4, 1, None) == ggml_hip.ERR_UNSUPPORTED  # (refused before any launch)
     for algo in (0, 1, 2, 4):
         assert mm(b.ptr, 64, 4, b.ptr, 1, b.ptr, 4, algo, None) == ggml_hip.OK
     ggml_hip.synchronize()
