@@ -100,6 +100,57 @@ int ggml_hip_debug_q8_0_auto_algo(int64_t K, int64_t M, int64_t N) { return debu
 
 int ggml_hip_debug_set_q8_0_gemm_min_n(int n) { return weight_type(gabi::TYPE_Q8_0)->min_n->set(n); }
 
+// Q4_1 / Q5_0 / Q5_1 (q5x_w.hip)
+static int dequantize_q5x(int type, const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
+    if (const int rc = check_dequantize(type, dev_wq, K, M, dev_w); rc != GGML_HIP_OK) return rc;
+    HIP_RET(ghip::dequantize_q5x(type != gabi::TYPE_Q4_1, type != gabi::TYPE_Q5_0, dev_wq, K, M, dev_w,
+                                 resolve_stream(stream)));
+    return GGML_HIP_OK;
+}
+
+int ggml_hip_dequantize_q4_1(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
+    return dequantize_q5x(gabi::TYPE_Q4_1, dev_wq, K, M, dev_w, stream);
+}
+
+int ggml_hip_dequantize_q5_0(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
+    return dequantize_q5x(gabi::TYPE_Q5_0, dev_wq, K, M, dev_w, stream);
+}
+
+int ggml_hip_dequantize_q5_1(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
+    return dequantize_q5x(gabi::TYPE_Q5_1, dev_wq, K, M, dev_w, stream);
+}
+
+int ggml_hip_mul_mat_q4_1(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N, float *dev_y,
+                          int64_t ldy, int algo, void *stream) {
+    return mul_mat_type(gabi::TYPE_Q4_1, dev_w, K, M, dev_x, N, dev_y, ldy, algo, stream);
+}
+
+int ggml_hip_mul_mat_q5_0(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N, float *dev_y,
+                          int64_t ldy, int algo, void *stream) {
+    return mul_mat_type(gabi::TYPE_Q5_0, dev_w, K, M, dev_x, N, dev_y, ldy, algo, stream);
+}
+
+int ggml_hip_mul_mat_q5_1(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N, float *dev_y,
+                          int64_t ldy, int algo, void *stream) {
+    return mul_mat_type(gabi::TYPE_Q5_1, dev_w, K, M, dev_x, N, dev_y, ldy, algo, stream);
+}
+
+int ggml_hip_quantize_q8_1(const float *dev_x, int64_t K, int64_t N, void *dev_xq, void *stream) {
+    if (!dev_x || !dev_xq || K <= 0 || K % QK || N < 0) return fail(GGML_HIP_ERR_INVALID, "bad arguments");
+    if (!aligned(dev_x, 16) || !aligned(dev_xq, 4))
+        return fail(GGML_HIP_ERR_INVALID, "x must be 16-byte aligned, the q8_1 rows 4-byte aligned");
+    HIP_RET(ghip::quantize_q8_1_aos(dev_x, K, N, dev_xq, resolve_stream(stream)));
+    return GGML_HIP_OK;
+}
+
+int ggml_hip_debug_q4_1_auto_algo(int64_t K, int64_t M, int64_t N) { return debug_auto_algo(gabi::TYPE_Q4_1, K, M, N); }
+
+int ggml_hip_debug_q5_0_auto_algo(int64_t K, int64_t M, int64_t N) { return debug_auto_algo(gabi::TYPE_Q5_0, K, M, N); }
+
+int ggml_hip_debug_q5_1_auto_algo(int64_t K, int64_t M, int64_t N) { return debug_auto_algo(gabi::TYPE_Q5_1, K, M, N); }
+
+int ggml_hip_debug_set_q5_0_gemm_min_n(int n) { return weight_type(gabi::TYPE_Q5_0)->min_n->set(n); }
+
 static int dequantize_q45k(int type, const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
     if (const int rc = check_dequantize(type, dev_wq, K, M, dev_w); rc != GGML_HIP_OK) return rc;
     ensure_init();
@@ -137,6 +188,12 @@ int ggml_hip_debug_set_q4_K(int on) { return q4k_set_enabled(on); }
 /* not in the public header: force the Q8_0 GEMV's launch policy (tests: every policy gives the same y bitwise) */
 int ggml_hip_debug_set_q8_0_gemv_policy(int map, int depth, int wg_per_cu) {
     ghip::gemv_q8_0w_set_policy(map, depth, wg_per_cu);
+    return GGML_HIP_OK;
+}
+
+/* not in the public header: the same for the Q4_1 / Q5_0 / Q5_1 GEMV (one policy for the three) */
+int ggml_hip_debug_set_q5x_gemv_policy(int map, int depth, int wg_per_cu) {
+    ghip::gemv_q5x_set_policy(map, depth, wg_per_cu);
     return GGML_HIP_OK;
 }
 
@@ -213,7 +270,7 @@ int ggml_hip_get_exact(void) { return exact_mode() ? 1 : 0; }
 int ggml_hip_reserve_workspace(int64_t K, int64_t N) {
     ensure_init();
     if (g_device_count == 0) return fail(GGML_HIP_ERR_DEVICE, "no HIP device");
-    return reserve_workspace(current_device(), workspace_bytes(K, N));
+    return reserve_workspace(current_device(), std::max(workspace_bytes(K, N), workspace_bytes_q81(K, N)));
 }
 
 int ggml_hip_weight_image_create(const void *dev_w, int64_t K, int64_t M, void *stream) {
@@ -261,7 +318,7 @@ int ggml_hip_reserve_workspace_mm(int64_t K, int64_t N, int64_t M) {
     ensure_init();
     if (g_device_count == 0) return fail(GGML_HIP_ERR_DEVICE, "no HIP device");
     if (K <= 0 || N < 0 || M < 0) return fail(GGML_HIP_ERR_INVALID, "bad shape");
-    return reserve_workspace(current_device(), workspace_bytes_mm(K, N, M));
+    return reserve_workspace(current_device(), std::max(workspace_bytes_mm(K, N, M), workspace_bytes_q81(K, N)));
 }
 
 // ------------------------------------------------------------------------------------------

@@ -326,13 +326,20 @@ int GemmMinN::set(int n) {
 static GemmMinN g_q6k_min_n{"GGML_HIP_Q6K_GEMM_MIN_N", 9};
 static GemmMinN g_q8_0_min_n{"GGML_HIP_Q8_0_GEMM_MIN_N", 32};
 static GemmMinN g_q45k_min_n{"GGML_HIP_Q45K_GEMM_MIN_N", 32};
+// Q5_0 (tools/q5x_bench.py, profiles/q5x_gemm.json; the three LLaMA-7B layer shapes, N = 9 .. 128): the GEMM arm is
+// flat in N (34-35 / 45-46 / 76-77 us, most of it the per-call image), the tiled GEMV wins at N = 9 and 16 on every
+// shape (4096 -> 11008 at N = 16: 44.8 against 44.9 us) and loses from N = 32 on every shape (4096 -> 4096: 45.6
+// against 34.9 us)
+static GemmMinN g_q5_0_min_n{"GGML_HIP_Q5_0_GEMM_MIN_N", 32};
 
 // the K a type's GEMV takes: one token's q8_K image in the LDS for the k-quants (w2 of a 30B / 65B model has K =
 // 17920 / 22016), one token's q8_0 for Q8_0
 static bool gemv_takes_k_kquant(int64_t K) { return K <= 16384; }
 static bool gemv_takes_k_q8_0(int64_t K) { return ghip::gemv_q8_0w_max_tokens(K) >= 1; }
+static bool gemv_takes_k_q5x(int64_t K) { return ghip::gemv_q5x_max_tokens(K) >= 1; }
 
 static MulMatSig mul_mat_q6k_dev, mul_mat_q8_0_dev, mul_mat_q5k_dev, mul_mat_q4k_dev;
+static MulMatSig mul_mat_q4_1_dev, mul_mat_q5_0_dev, mul_mat_q5_1_dev;
 
 static constexpr const char *ERR_K256 = "K must be a multiple of 256 (QK_K)";
 static constexpr const char *ERR_ALIGN_Q45K = "W and x must be 16-byte, y 4-byte aligned";
@@ -366,8 +373,36 @@ static const WeightType ROW_Q4_K = {
     ERR_K256, ERR_ALIGN_Q45K, ERR_GEMV_Q45K,
     QK_K, 16, ERR_DQ_Q45K};
 
+// Q4_1 / Q5_0 / Q5_1 (q5x_w.hip).  Q5_0's values q - 16 are int8 and its activations q8_0, so it takes Q8_0's GEMM
+// (algo 2).  Q4_1 and Q5_1 have no GEMM: their activation scale is an unrounded f32, which k_gemm8's fp16 d_x plane
+// cannot carry.  Their rows name the GEMV as the GEMM algo, so auto_algo's one expression never leaves it whatever
+// the threshold says, and prefill runs as column tiles of the GEMV; where the GEMV cannot take K they run the exact
+// kernel, which has no K limit.
+static constexpr const char *ERR_K64_Q5X = "K must be a multiple of 64 (ggml.c:2614, 2740, 2980 nb % 2 == 0)";
+static constexpr const char *ERR_ALIGN_Q5X = "W must be 4-byte, x 16-byte, y 4-byte aligned";
+static constexpr const char *ERR_GEMV_Q5X = "K too long for the Q4_1 / Q5_0 / Q5_1 GEMV";
+static constexpr const char *ERR_DQ_Q5X = "w must be 16-byte aligned, the Q4_1 / Q5_0 / Q5_1 rows 4-byte aligned";
+static const WeightType ROW_Q4_1 = {
+    64, 4, 1 << 30,
+    1, 4, &g_q5_0_min_n, gemv_takes_k_q5x, mul_mat_q4_1_dev,
+    ERR_K64_Q5X, ERR_ALIGN_Q5X, ERR_GEMV_Q5X,
+    64, 4, ERR_DQ_Q5X};
+static const WeightType ROW_Q5_0 = {
+    64, 4, 1 << 30,
+    2, 2, &g_q5_0_min_n, gemv_takes_k_q5x, mul_mat_q5_0_dev,
+    ERR_K64_Q5X, ERR_ALIGN_Q5X, ERR_GEMV_Q5X,
+    64, 4, ERR_DQ_Q5X};
+static const WeightType ROW_Q5_1 = {
+    64, 4, 1 << 30,
+    1, 4, &g_q5_0_min_n, gemv_takes_k_q5x, mul_mat_q5_1_dev,
+    ERR_K64_Q5X, ERR_ALIGN_Q5X, ERR_GEMV_Q5X,
+    64, 4, ERR_DQ_Q5X};
+
 const WeightType *weight_type(int type) {
     switch (type) {
+        case gabi::TYPE_Q4_1: return &ROW_Q4_1;
+        case gabi::TYPE_Q5_0: return &ROW_Q5_0;
+        case gabi::TYPE_Q5_1: return &ROW_Q5_1;
         case gabi::TYPE_Q6_K: return &ROW_Q6_K;
         case gabi::TYPE_Q8_0: return &ROW_Q8_0;
         case gabi::TYPE_Q5_K: return &ROW_Q5_K;
@@ -481,6 +516,62 @@ static int mul_mat_q8_0_dev(const void *w, int64_t K, int64_t M, const float *x,
     HIP_RET(ghip::quantize_q8_0_soa(x, K, N, qs, xd, s));
     HIP_RET(ghip::mm_exact_q8_0w(w, K, M, qs, xd, N, y, ldy, s));
     return GGML_HIP_OK;
+}
+
+// Q4_1 / Q5_0 / Q5_1 (q5x_w.hip): algo 2 (Q5_0 only) = the k_gemm8 image of q - 16 built per call into the workspace
+// (k_prep8_w_q5_0), then gemm8_prep_x + gemm8_run unchanged, as Q8_0; algo 4 = the SoA quantizer (q8_0's planes for
+// Q5_0; q8_1's qs, d and s for the types with a minimum, workspace_bytes_q81) + the exact kernel
+size_t workspace_bytes_q81(int64_t K, int64_t N) {
+    const size_t plane = ((size_t)N * (K / QK) * 4 + 255) & ~(size_t)255;
+    return (((size_t)(N * K) + 255) & ~(size_t)255) + 2 * plane;
+}
+static int mul_mat_q5x_dev(const WeightType &t, bool qh, bool mn, const void *w, int64_t K, int64_t M, const float *x,
+                           int64_t N, float *y, int64_t ldy, int algo, hipStream_t s) {
+    const int rc = check_operands(t, w, K, M, x, N, y, ldy);
+    if (rc != GGML_HIP_OK || N == 0) return rc;
+    const int id = current_device();
+    if (algo == 0) algo = auto_algo(t, K, N);
+    if (algo == 1) {
+        if (!t.gemv_takes_k(K)) return fail(GGML_HIP_ERR_UNSUPPORTED, t.err_gemv_k);
+        HIP_RET(ghip::gemv_q5x(qh, mn, w, K, M, x, N, y, ldy, g_dev[id].info, s));
+        return GGML_HIP_OK;
+    }
+    if (algo != 4 && !(algo == 2 && !mn))
+        return fail(GGML_HIP_ERR_INVALID, mn ? "algo must be 0, 1 or 4" : "algo must be 0, 1, 2 or 4");
+    void *ws = nullptr;
+    if (algo == 2) {
+        if ((N + 7) / 8 > 65535) return fail(GGML_HIP_ERR_UNSUPPORTED, "too many columns for one launch; split columns");
+        const int wrc = stream_workspace(id, s, workspace_bytes_mm(K, N, M), &ws);
+        if (wrc != GGML_HIP_OK) return wrc;
+        void *xws = (char *)ws + ws_g8x_offset(K, N), *wws = (char *)ws + ws_g8w_offset(K, N);
+        HIP_RET(ghip::gemm8_prep_x(x, K, N, xws, s));
+        HIP_RET(ghip::gemm8_prep_w_q5_0(w, K, M, wws, s));
+        HIP_RET(ghip::gemm8_run(wws, K, M, xws, N, y, ldy, s));
+        return GGML_HIP_OK;
+    }
+    const int wrc = stream_workspace(id, s, mn ? workspace_bytes_q81(K, N) : workspace_bytes(K, N), &ws);
+    if (wrc != GGML_HIP_OK) return wrc;
+    int8_t *qs = (int8_t *)ws;
+    float *xd = (float *)((char *)ws + ((size_t)(N * K + 255) & ~(size_t)255));
+    float *xs = (float *)((char *)xd + (((size_t)N * (K / QK) * 4 + 255) & ~(size_t)255));
+    if (mn)
+        HIP_RET(ghip::quantize_q8_1_soa(x, K, N, qs, xd, xs, s));
+    else
+        HIP_RET(ghip::quantize_q8_0_soa(x, K, N, qs, xd, s));
+    HIP_RET(ghip::mm_exact_q5x(qh, mn, w, K, M, qs, xd, xs, N, y, ldy, s));
+    return GGML_HIP_OK;
+}
+static int mul_mat_q4_1_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                            hipStream_t s) {
+    return mul_mat_q5x_dev(ROW_Q4_1, false, true, w, K, M, x, N, y, ldy, algo, s);
+}
+static int mul_mat_q5_0_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                            hipStream_t s) {
+    return mul_mat_q5x_dev(ROW_Q5_0, true, false, w, K, M, x, N, y, ldy, algo, s);
+}
+static int mul_mat_q5_1_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                            hipStream_t s) {
+    return mul_mat_q5x_dev(ROW_Q5_1, true, true, w, K, M, x, N, y, ldy, algo, s);
 }
 
 // Q5_K (qh) / Q4_K (q45_k.hip, q45_k_gemm.hip): algo 6 = the q8_K values of x and their sub-block sums' digits as

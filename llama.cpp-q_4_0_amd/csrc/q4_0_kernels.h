@@ -189,6 +189,29 @@ hipError_t quantize_q8_K_digit_planes(const float *x, int64_t K, int64_t N, void
 hipError_t gemm_q45_K(bool qh, const void *W, int64_t K, int64_t M, const void *xqs, const float *xd, const void *xdig,
                       int64_t N, float *y, int64_t ldy, const DeviceInfo &dev, hipStream_t s);
 
+// Q4_1 / Q5_0 / Q5_1 weights (q5x_w.hip): the layer matrices of a "mostly Q4_1 / Q5_0 / Q5_1" file.  W: ggml
+// block_q4_1 (20 bytes per 32 weights), block_q5_0 (22) or block_q5_1 (24) rows, verbatim, 4-byte aligned (K % 64
+// == 0); qh: the type has a fifth bit plane (Q5_0, Q5_1), mn: a minimum and q8_1 activations (Q4_1, Q5_1).
+// dequantize_row_q4_1 / _q5_0 / _q5_1, bit-exact
+hipError_t dequantize_q5x(bool qh, bool mn, const void *wq, int64_t K, int64_t M, float *w, hipStream_t s);
+// quantize_row_q8_1 (AVX2 branch), bit-exact: block_q8_1 rows (40 bytes per 32 elements), or the planes qs int8
+// [N][K], d f32 [N][K / 32], s f32 [N][K / 32]
+hipError_t quantize_q8_1_aos(const float *x, int64_t K, int64_t N, void *xq, hipStream_t s);
+hipError_t quantize_q8_1_soa(const float *x, int64_t K, int64_t N, int8_t *qs, float *d, float *sx, hipStream_t s);
+// fused quantize of x (LDS, 40 bytes per block and token) + GEMV; N > gemv_q5x_max_tokens(K) runs column tiles (a
+// column's y does not depend on its tile); max_tokens is 8 up to K = 6528 and 0 where one token exceeds the LDS
+int gemv_q5x_max_tokens(int64_t K);
+hipError_t gemv_q5x(bool qh, bool mn, const void *W, int64_t K, int64_t M, const float *x, int64_t N, float *y,
+                    int64_t ldy, const DeviceInfo &dev, hipStream_t s);
+// test hook: force the launch policy (row mapping -1 auto / 0 / 1 / 2, ring depth 0 auto / 1 / 2, workgroups per CU)
+void gemv_q5x_set_policy(int map, int depth, int wg_per_cu);
+// exact mode: y bit-identical to the type's AVX2 ggml_vec_dot on the planes of x: quantize_q8_0_soa's qs and d for
+// Q5_0 (xsum unused), quantize_q8_1_soa's for the other two; any N, no K limit
+hipError_t mm_exact_q5x(bool qh, bool mn, const void *W, int64_t K, int64_t M, const int8_t *xqs, const float *xd,
+                        const float *xsum, int64_t N, float *y, int64_t ldy, hipStream_t s);
+// Q5_0 prefill: the k_gemm8 weight image (gemm8_w_bytes(K, M) bytes) of q - 16; then gemm8_prep_x + gemm8_run
+hipError_t gemm8_prep_w_q5_0(const void *W, int64_t K, int64_t M, void *wws, hipStream_t s);
+
 // Multi-GPU helper: y[n*ldy + row0[r] + i] = slab[r][n][i] for i < rows[r] (gather compaction).
 // row_begin travels as a kernel argument (no host->device copy, capture-safe)
 static constexpr int SCATTER_MAX_RANKS = 256;

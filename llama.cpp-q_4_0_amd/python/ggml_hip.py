@@ -71,6 +71,18 @@ def _bind(L):
         "ggml_hip_debug_set_q45k_gemm_min_n": ([i32], i32),
         "ggml_hip_debug_q8_0_auto_algo": ([i64, i64, i64], i32),
         "ggml_hip_debug_set_q8_0_gemm_min_n": ([i32], i32),
+        "ggml_hip_dequantize_q4_1": ([vp, i64, i64, vp, vp], i32),
+        "ggml_hip_dequantize_q5_0": ([vp, i64, i64, vp, vp], i32),
+        "ggml_hip_dequantize_q5_1": ([vp, i64, i64, vp, vp], i32),
+        "ggml_hip_quantize_q8_1": ([vp, i64, i64, vp, vp], i32),
+        "ggml_hip_mul_mat_q4_1": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
+        "ggml_hip_mul_mat_q5_0": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
+        "ggml_hip_mul_mat_q5_1": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
+        "ggml_hip_debug_q4_1_auto_algo": ([i64, i64, i64], i32),
+        "ggml_hip_debug_q5_0_auto_algo": ([i64, i64, i64], i32),
+        "ggml_hip_debug_q5_1_auto_algo": ([i64, i64, i64], i32),
+        "ggml_hip_debug_set_q5_0_gemm_min_n": ([i32], i32),
+        "ggml_hip_debug_set_q5x_gemv_policy": ([i32, i32, i32], i32),
         "ggml_hip_reserve_workspace": ([i64, i64], i32),
         "ggml_hip_reserve_workspace_mm": ([i64, i64, i64], i32),
         "ggml_hip_weight_image_create": ([vp, i64, i64, vp], i32),
@@ -294,6 +306,40 @@ def mul_mat_q8_0(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_
     _mul_mat_typed("mul_mat_q8_0", w_dev, K, M, x_dev, N, y_dev, algo, ldy, stream, w_off, x_off, y_off)
 
 
+def quantize_q8_1(x_dev, K, N, xq_dev, stream=None):
+    """f32 [N][K] -> block_q8_1 rows (f32 d, f32 s, qs[32]: 40 * K / 32 bytes each), bit-exact."""
+    check(load().ggml_hip_quantize_q8_1(_ptr(x_dev), K, N, _ptr(xq_dev), stream), "quantize_q8_1")
+
+
+def dequantize_q4_1(wq_dev, K, M, w_dev, stream=None):
+    check(load().ggml_hip_dequantize_q4_1(_ptr(wq_dev), K, M, _ptr(w_dev), stream), "dequantize_q4_1")
+
+
+def dequantize_q5_0(wq_dev, K, M, w_dev, stream=None):
+    check(load().ggml_hip_dequantize_q5_0(_ptr(wq_dev), K, M, _ptr(w_dev), stream), "dequantize_q5_0")
+
+
+def dequantize_q5_1(wq_dev, K, M, w_dev, stream=None):
+    check(load().ggml_hip_dequantize_q5_1(_ptr(wq_dev), K, M, _ptr(w_dev), stream), "dequantize_q5_1")
+
+
+def mul_mat_q4_1(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_off=0, x_off=0, y_off=0):
+    """Q4_1 rows (20 * K / 32 bytes each, 4-byte aligned) x f32 [N][K] -> f32 y[n * ldy + m]; algo 0 auto (exact mode,
+    or K too long for the GEMV: 4; else 1), 1 GEMV (column tiles), 4 exact.  No GEMM: 2 is invalid."""
+    _mul_mat_typed("mul_mat_q4_1", w_dev, K, M, x_dev, N, y_dev, algo, ldy, stream, w_off, x_off, y_off)
+
+
+def mul_mat_q5_0(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_off=0, x_off=0, y_off=0):
+    """Q5_0 rows (22 * K / 32 bytes each, 4-byte aligned) x f32 [N][K] -> f32 y[n * ldy + m]; algo 0 auto (exact mode:
+    4; N below the GEMM threshold: 1; else 2), 1 GEMV, 2 per-call int8 image + int8-MFMA GEMM, 4 exact."""
+    _mul_mat_typed("mul_mat_q5_0", w_dev, K, M, x_dev, N, y_dev, algo, ldy, stream, w_off, x_off, y_off)
+
+
+def mul_mat_q5_1(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_off=0, x_off=0, y_off=0):
+    """Q5_1 rows (24 * K / 32 bytes each, 4-byte aligned) x f32 [N][K] -> f32 y[n * ldy + m]; algos as mul_mat_q4_1."""
+    _mul_mat_typed("mul_mat_q5_1", w_dev, K, M, x_dev, N, y_dev, algo, ldy, stream, w_off, x_off, y_off)
+
+
 def dequantize_q5_K(wq_dev, K, M, w_dev, stream=None):
     check(load().ggml_hip_dequantize_q5_K(_ptr(wq_dev), K, M, _ptr(w_dev), stream), "dequantize_q5_K")
 
@@ -440,6 +486,7 @@ class Graph:
 GGML_TYPE_F32, GGML_TYPE_Q4_0 = 0, 2
 GGML_TYPE_Q6_K = 14
 GGML_TYPE_Q8_0 = 8
+GGML_TYPE_Q4_1, GGML_TYPE_Q5_0, GGML_TYPE_Q5_1 = 3, 6, 7
 GGML_TYPE_Q4_K, GGML_TYPE_Q5_K = 12, 13
 GGML_BACKEND_CPU, GGML_BACKEND_GPU, GGML_BACKEND_GPU_SPLIT = 0, 10, 20
 GGML_OP_MUL_MAT = 32
@@ -484,6 +531,9 @@ def make_tensor(gtype, ne, data=None, backend=GGML_BACKEND_CPU):
     elif gtype == GGML_TYPE_Q8_0:
         t.nb[0] = 34
         t.nb[1] = 34 * ne[0] // 32
+    elif gtype in (GGML_TYPE_Q4_1, GGML_TYPE_Q5_0, GGML_TYPE_Q5_1):
+        t.nb[0] = {GGML_TYPE_Q4_1: 20, GGML_TYPE_Q5_0: 22, GGML_TYPE_Q5_1: 24}[gtype]
+        t.nb[1] = t.nb[0] * ne[0] // 32
     elif gtype in (GGML_TYPE_Q5_K, GGML_TYPE_Q4_K):
         t.nb[0] = 176 if gtype == GGML_TYPE_Q5_K else 144
         t.nb[1] = t.nb[0] * ne[0] // 256
