@@ -201,8 +201,8 @@ int ggml_hip_debug_set_q8_0_gemm_min_n(int n);
 /* Q4_1 / Q5_0 / Q5_1 WEIGHTS (block_q4_1 rows, 20 bytes per 32 weights; block_q5_0, 22; block_q5_1, 24; dev_w 4-byte
  * aligned, K % 64 == 0 so every row is) x F32 -> F32 with the semantics of ggml_vec_dot_q4_1_q8_1 /
  * ggml_vec_dot_q5_0_q8_0 / ggml_vec_dot_q5_1_q8_1 on the bit-exact q8_1 (Q4_1, Q5_1) or q8_0 (Q5_0) of x.
- * Stream-ordered and graph-capturable once ggml_hip_reserve_workspace(K, N) has run (the exact mode's planes of x, 40
- * bytes per 32 elements for q8_1) or, for Q5_0's GEMM, ggml_hip_reserve_workspace_mm(K, N, M).  No byte outside the
+ * Stream-ordered and graph-capturable once ggml_hip_reserve_workspace(K, N) has run (the planes of x of the exact
+ * mode and of the Q4_1 / Q5_1 GEMM, 40 bytes per 32 elements for q8_1) or, for Q5_0's GEMM, ggml_hip_reserve_workspace_mm(K, N, M).  No byte outside the
  * matrix is read.  Status codes as for ggml_hip_mul_mat_q8_0; N = 0 -> GGML_HIP_OK.
  * dequantize_q4_1 / _q5_0 / _q5_1: dequantize_row_q4_1 / _q5_0 / _q5_1 (ggml.c:1520-1592), bit-exact. */
 int ggml_hip_dequantize_q4_1(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream);
@@ -212,19 +212,24 @@ int ggml_hip_dequantize_q5_1(const void *dev_wq, int64_t K, int64_t M, float *de
  * aligned); bit-exact to quantize_row_q8_1's AVX2 branch (ggml.c:1402-1463). */
 int ggml_hip_quantize_q8_1(const float *dev_x, int64_t K, int64_t N, void *dev_xq, void *stream);
 /* y[n*ldy + m] = W[m] . x[n].  algo: 0 auto (4 in exact mode and where K is too long for the GEMV on Q4_1 / Q5_1;
- * Q5_0: 2 from the GEMM threshold and where K is too long for the GEMV; else 1), 1 GEMV with the quantization of x
+ * Q5_0: 2 from the GEMM threshold and where K is too long for the GEMV; Q4_1 / Q5_1: 7 from their GEMM threshold,
+ * whose default is "never"; else 1), 1 GEMV with the quantization of x
  * fused in (column tiles of 8 for N > 8, fewer above K = 6528, GGML_HIP_ERR_UNSUPPORTED where one token does not fit
  * the LDS; a column's y is bitwise the same in every tile and under every launch policy), 2 (Q5_0 only) the int8
  * image of q - 16 built per call into the workspace, then the int8-MFMA GEMM of the q4_0 path (k_gemm8) unchanged,
  * 4 exact: bit-identical to the AVX2 branch of the type's ggml_vec_dot (ggml.c:2680-2713, 2894-2916, 3144-3169), no
- * K limit.  Anything else (2 on Q4_1 / Q5_1 included) -> GGML_HIP_ERR_INVALID. */
+ * K limit, 7 (Q4_1 / Q5_1 only) prefill GEMM on the int8 matrix cores (any K % 64 == 0, any N >= 1): the blocks read
+ * in place, x quantized to q8_1 planes into the workspace; per output one fp32 chain over the blocks in order, acc =
+ * fma((float)isum_b, d_w * d_x, acc) then acc = fma(m_w, s_x, acc) with the exact integer block sum isum_b, so y
+ * depends on (row, column, K) alone and is within the parity bound of algo 1's, not bitwise it.  Anything else (2 on
+ * Q4_1 / Q5_1 and 7 on Q5_0 included) -> GGML_HIP_ERR_INVALID. */
 int ggml_hip_mul_mat_q4_1(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N,
                           float *dev_y, int64_t ldy, int algo, void *stream);
 int ggml_hip_mul_mat_q5_0(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N,
                           float *dev_y, int64_t ldy, int algo, void *stream);
 int ggml_hip_mul_mat_q5_1(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N,
                           float *dev_y, int64_t ldy, int algo, void *stream);
-/* debug, no device needed: the algo that algo 0 of the type's mul_mat would run now: 1 or 4 (Q5_0: 1, 2 or 4) */
+/* debug, no device needed: the algo that algo 0 of the type's mul_mat would run now: 1, 4 or 7 (Q5_0: 1, 2 or 4) */
 int ggml_hip_debug_q4_1_auto_algo(int64_t K, int64_t M, int64_t N);
 int ggml_hip_debug_q5_0_auto_algo(int64_t K, int64_t M, int64_t N);
 int ggml_hip_debug_q5_1_auto_algo(int64_t K, int64_t M, int64_t N);
@@ -232,6 +237,10 @@ int ggml_hip_debug_q5_1_auto_algo(int64_t K, int64_t M, int64_t N);
  * shapes; GGML_HIP_Q5_0_GEMM_MIN_N; values below 9 count as 9); -1 restores the environment value or the default.
  * Returns the previous value. */
 int ggml_hip_debug_set_q5_0_gemm_min_n(int n);
+/* debug: the smallest N at which auto takes the Q4_1 / Q5_1 GEMM (algo 7).  Default INT_MAX: never, auto runs the
+ * GEMV at every N; GGML_HIP_Q41_Q51_GEMM_MIN_N switches it on (the measured crossover is in DESIGN.md section 4b);
+ * values below 9 count as 9; -1 restores the environment value or the default.  Returns the previous value. */
+int ggml_hip_debug_set_q41_q51_gemm_min_n(int n);
 /* Q5_K / Q4_K WEIGHTS (block_q5_K rows, 176 bytes per 256 weights; block_q4_K rows, 144 bytes; dev_w 16-byte
  * aligned, so every block and row is) x F32 -> F32 with the semantics of ggml_vec_dot_q5_K_q8_K /
  * ggml_vec_dot_q4_K_q8_K on the bit-exact q8_K of x.  K % 256 == 0.  Stream-ordered and capturable (exact mode

@@ -151,6 +151,8 @@ int ggml_hip_debug_q5_1_auto_algo(int64_t K, int64_t M, int64_t N) { return debu
 
 int ggml_hip_debug_set_q5_0_gemm_min_n(int n) { return weight_type(gabi::TYPE_Q5_0)->min_n->set(n); }
 
+int ggml_hip_debug_set_q41_q51_gemm_min_n(int n) { return weight_type(gabi::TYPE_Q5_1)->min_n->set(n); }
+
 static int dequantize_q45k(int type, const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
     if (const int rc = check_dequantize(type, dev_wq, K, M, dev_w); rc != GGML_HIP_OK) return rc;
     ensure_init();

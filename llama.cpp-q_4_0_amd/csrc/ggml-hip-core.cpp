@@ -297,7 +297,10 @@ int mul_mat_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, 
 // The weight types beside Q4_0: one row each (WeightType, ggml-hip-internal.h).  A type's mul_mat has algo 0 auto
 // (auto_algo), 1 the fused GEMV in column tiles, 4 the exact kernel and the type's own GEMM algo; the GEMM's y is
 // bit for bit the GEMV's on the k-quants (the same exact integer superblock sums, the same fp32 step per
-// superblock in the same order), so the switch between the two never changes a result.
+// superblock in the same order), so the switch between the two never changes a result.  On Q8_0, Q5_0, Q4_1 and
+// Q5_1 it is not: the GEMV adds a row's blocks as 64 lane chains and a tree, the GEMMs as one chain per output (Q4_1
+// / Q5_1, algo 7) or k_gemm8's order (Q8_0, Q5_0), so there the switch between GEMV and GEMM moves a result within
+// the parity bound.
 
 int GemmMinN::get() {
     int n = v.load(std::memory_order_relaxed);
@@ -331,6 +334,9 @@ static GemmMinN g_q45k_min_n{"GGML_HIP_Q45K_GEMM_MIN_N", 32};
 // shape (4096 -> 11008 at N = 16: 44.8 against 44.9 us) and loses from N = 32 on every shape (4096 -> 4096: 45.6
 // against 34.9 us)
 static GemmMinN g_q5_0_min_n{"GGML_HIP_Q5_0_GEMM_MIN_N", 32};
+// Q4_1 / Q5_1 (algo 7, q5x_gemm.hip): "never" by default, so auto runs the GEMV at every N until the user sets the
+// threshold (the measured crossover is in DESIGN §4b; tools/q5x_bench.py, profiles/q5x1_gemm.json)
+static GemmMinN g_q41_q51_min_n{"GGML_HIP_Q41_Q51_GEMM_MIN_N", INT_MAX};
 
 // the K a type's GEMV takes: one token's q8_K image in the LDS for the k-quants (w2 of a 30B / 65B model has K =
 // 17920 / 22016), one token's q8_0 for Q8_0
@@ -374,17 +380,18 @@ static const WeightType ROW_Q4_K = {
     QK_K, 16, ERR_DQ_Q45K};
 
 // Q4_1 / Q5_0 / Q5_1 (q5x_w.hip).  Q5_0's values q - 16 are int8 and its activations q8_0, so it takes Q8_0's GEMM
-// (algo 2).  Q4_1 and Q5_1 have no GEMM: their activation scale is an unrounded f32, which k_gemm8's fp16 d_x plane
-// cannot carry.  Their rows name the GEMV as the GEMM algo, so auto_algo's one expression never leaves it whatever
-// the threshold says, and prefill runs as column tiles of the GEMV; where the GEMV cannot take K they run the exact
-// kernel, which has no K limit.
+// (algo 2).  Q4_1 and Q5_1 cannot: their activation scale is an unrounded f32 and they carry a second term m_w s_x
+// per block, which k_gemm8's fp16 d_x plane and single-term epilogue do not hold.  They have a GEMM of their own on
+// the weights in place (algo 7, k_gemm_q5x1) behind a threshold of their own whose default is "never": until it is
+// set, prefill runs as column tiles of the GEMV.  Where the GEMV cannot take K they run the exact kernel, which has
+// no K limit.
 static constexpr const char *ERR_K64_Q5X = "K must be a multiple of 64 (ggml.c:2614, 2740, 2980 nb % 2 == 0)";
 static constexpr const char *ERR_ALIGN_Q5X = "W must be 4-byte, x 16-byte, y 4-byte aligned";
 static constexpr const char *ERR_GEMV_Q5X = "K too long for the Q4_1 / Q5_0 / Q5_1 GEMV";
 static constexpr const char *ERR_DQ_Q5X = "w must be 16-byte aligned, the Q4_1 / Q5_0 / Q5_1 rows 4-byte aligned";
 static const WeightType ROW_Q4_1 = {
     64, 4, 1 << 30,
-    1, 4, &g_q5_0_min_n, gemv_takes_k_q5x, mul_mat_q4_1_dev,
+    7, 4, &g_q41_q51_min_n, gemv_takes_k_q5x, mul_mat_q4_1_dev,
     ERR_K64_Q5X, ERR_ALIGN_Q5X, ERR_GEMV_Q5X,
     64, 4, ERR_DQ_Q5X};
 static const WeightType ROW_Q5_0 = {
@@ -394,7 +401,7 @@ static const WeightType ROW_Q5_0 = {
     64, 4, ERR_DQ_Q5X};
 static const WeightType ROW_Q5_1 = {
     64, 4, 1 << 30,
-    1, 4, &g_q5_0_min_n, gemv_takes_k_q5x, mul_mat_q5_1_dev,
+    7, 4, &g_q41_q51_min_n, gemv_takes_k_q5x, mul_mat_q5_1_dev,
     ERR_K64_Q5X, ERR_ALIGN_Q5X, ERR_GEMV_Q5X,
     64, 4, ERR_DQ_Q5X};
 
@@ -520,7 +527,9 @@ static int mul_mat_q8_0_dev(const void *w, int64_t K, int64_t M, const float *x,
 
 // Q4_1 / Q5_0 / Q5_1 (q5x_w.hip): algo 2 (Q5_0 only) = the k_gemm8 image of q - 16 built per call into the workspace
 // (k_prep8_w_q5_0), then gemm8_prep_x + gemm8_run unchanged, as Q8_0; algo 4 = the SoA quantizer (q8_0's planes for
-// Q5_0; q8_1's qs, d and s for the types with a minimum, workspace_bytes_q81) + the exact kernel
+// Q5_0; q8_1's qs, d and s for the types with a minimum, workspace_bytes_q81) + the exact kernel; algo 7 (the types
+// with a minimum only, any N >= 1, no K limit) = the same q8_1 planes + k_gemm_q5x1 on the weights in place
+// (q5x_gemm.hip)
 size_t workspace_bytes_q81(int64_t K, int64_t N) {
     const size_t plane = ((size_t)N * (K / QK) * 4 + 255) & ~(size_t)255;
     return (((size_t)(N * K) + 255) & ~(size_t)255) + 2 * plane;
@@ -536,8 +545,9 @@ static int mul_mat_q5x_dev(const WeightType &t, bool qh, bool mn, const void *w,
         HIP_RET(ghip::gemv_q5x(qh, mn, w, K, M, x, N, y, ldy, g_dev[id].info, s));
         return GGML_HIP_OK;
     }
-    if (algo != 4 && !(algo == 2 && !mn))
-        return fail(GGML_HIP_ERR_INVALID, mn ? "algo must be 0, 1 or 4" : "algo must be 0, 1, 2 or 4");
+    if (algo != 4 && algo != (mn ? 7 : 2))
+        return fail(GGML_HIP_ERR_INVALID, mn ? "algo must be 0, 1, 4 or 7" : "algo must be 0, 1, 2 or 4");
+    if (algo == 7 && too_many_tiles(M, N)) return fail(GGML_HIP_ERR_UNSUPPORTED, ERR_TILES);
     void *ws = nullptr;
     if (algo == 2) {
         if ((N + 7) / 8 > 65535) return fail(GGML_HIP_ERR_UNSUPPORTED, "too many columns for one launch; split columns");
@@ -558,7 +568,10 @@ static int mul_mat_q5x_dev(const WeightType &t, bool qh, bool mn, const void *w,
         HIP_RET(ghip::quantize_q8_1_soa(x, K, N, qs, xd, xs, s));
     else
         HIP_RET(ghip::quantize_q8_0_soa(x, K, N, qs, xd, s));
-    HIP_RET(ghip::mm_exact_q5x(qh, mn, w, K, M, qs, xd, xs, N, y, ldy, s));
+    if (algo == 7)
+        HIP_RET(ghip::gemm_q5x1(qh, w, K, M, qs, xd, xs, N, y, ldy, g_dev[id].info, s));
+    else
+        HIP_RET(ghip::mm_exact_q5x(qh, mn, w, K, M, qs, xd, xs, N, y, ldy, s));
     return GGML_HIP_OK;
 }
 static int mul_mat_q4_1_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,

@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <condition_variable>
 #include <cstdio>
@@ -138,7 +139,7 @@ void *pool_malloc(int id, size_t size, size_t *actual);
 void pool_free(int id, void *p, size_t size);
 size_t ws_d16_offset(int64_t K, int64_t N);
 size_t workspace_bytes(int64_t K, int64_t N);
-size_t workspace_bytes_q81(int64_t K, int64_t N);     // the exact arm of Q4_1 / Q5_1: q8_1 planes, 40 B per block
+size_t workspace_bytes_q81(int64_t K, int64_t N);     // the exact and GEMM arms of Q4_1 / Q5_1: q8_1 planes, 40 B per block
 size_t ws_g8x_offset(int64_t K, int64_t N);
 size_t ws_g8w_offset(int64_t K, int64_t N);
 size_t workspace_bytes_mm(int64_t K, int64_t N, int64_t M);

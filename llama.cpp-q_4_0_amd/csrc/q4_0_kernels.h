@@ -211,6 +211,11 @@ hipError_t mm_exact_q5x(bool qh, bool mn, const void *W, int64_t K, int64_t M, c
                         const float *xsum, int64_t N, float *y, int64_t ldy, hipStream_t s);
 // Q5_0 prefill: the k_gemm8 weight image (gemm8_w_bytes(K, M) bytes) of q - 16; then gemm8_prep_x + gemm8_run
 hipError_t gemm8_prep_w_q5_0(const void *W, int64_t K, int64_t M, void *wws, hipStream_t s);
+// Q4_1 / Q5_1 prefill (q5x_gemm.hip): the int8-MFMA GEMM on the weights in place and quantize_q8_1_soa's planes of x
+// (qs 16-byte, d and sx 8-byte aligned); one fp32 chain per output, block by block (y within the parity bound of
+// gemv_q5x's, not bitwise it); any K % 64 == 0 (N K < 2^31), M, N >= 1
+hipError_t gemm_q5x1(bool qh, const void *W, int64_t K, int64_t M, const int8_t *xqs, const float *xd, const float *xsum,
+                     int64_t N, float *y, int64_t ldy, const DeviceInfo &dev, hipStream_t s);
 
 // Multi-GPU helper: y[n*ldy + row0[r] + i] = slab[r][n][i] for i < rows[r] (gather compaction).
 // row_begin travels as a kernel argument (no host->device copy, capture-safe)

@@ -1,7 +1,8 @@
 // q5x_w.hip — Q4_1, Q5_0 and Q5_1 WEIGHTS x F32 mul_mat (gfx950, wave64): the layer matrices of the "mostly Q4_1 /
 // Q5_0 / Q5_1" files.  One kernel family, templates over <QH, MIN>: QH = the block has a fifth bit plane qh (Q5_0,
 // Q5_1), MIN = it has a minimum m and multiplies against q8_1 activations (Q4_1, Q5_1).  Shared device helpers:
-// q4_0_device.h.  What each kernel restates (reference = ggml.c of Fcucgvhhhvjv/llama.cpp-q_4_0):
+// q4_0_device.h and q5x_device.h (a block pair's load and decode, shared with the Q4_1 / Q5_1 prefill GEMM
+// q5x_gemm.hip).  What each kernel restates (reference = ggml.c of Fcucgvhhhvjv/llama.cpp-q_4_0):
 //   k_dequantize_q5x    dequantize_row_q4_1 / q5_0 / q5_1 ggml.c:1520-1592 (bit-exact: one multiply, one add for MIN)
 //   k_quantize_q8_1     quantize_row_q8_1, AVX2 branch ggml.c:1402-1463 (bit-exact: q8_0's bytes, d = amax / 127.f
 //                       kept as f32, s = d * (float)sum q)
@@ -23,23 +24,9 @@
 //
 // Numerics: a block's integer sum is eight v_dot4_i32_i8 on the UNSIGNED 4 / 5-bit values (at most 32 * 31 * 127 <
 // 2^17, exact); Q5_0's offset is applied once per block as -16 * sum q_x.
-#include "q4_0_device.h"
+#include "q5x_device.h"
 
 namespace ghip {
-
-template <bool QH, bool MIN>
-struct Q5x {
-    static constexpr int BLK = 18 + 2 * MIN + 4 * QH;     // 20 / 22 / 24
-    static constexpr int PAIR = 2 * BLK;                  // 40 / 44 / 48
-    static constexpr int DW = PAIR / 4;
-    static constexpr int OFF_QH = 2 + 2 * MIN, OFF_QS = OFF_QH + 4 * QH;
-};
-
-// the four bits b of a nibble -> bit 4 of byte k for bit k (b * 0x204081 puts bit k at 8 k among others: the
-// sixteen partial positions are distinct, so nothing carries)
-__device__ __forceinline__ uint32_t q5x_spread4(uint32_t qh, int shift) {
-    return ((((qh >> shift) & 0xFu) * 0x00204081u) & 0x01010101u) << 4;
-}
 
 // four bytes at a 2-byte aligned address from the aligned dwords that hold them (one dword when p is aligned)
 __device__ __forceinline__ uint32_t q5x_ld32(const uint8_t *p) {
@@ -153,83 +140,6 @@ static constexpr int G5X_WAVES = 16;
 static constexpr int G5X_LDS_MAX = 64 * 1024;
 static constexpr int G5X_XPRO = 4;            // x float4 loads in flight per x-wave thread
 static constexpr int G5X_XBYTES = 40;         // LDS bytes per block and token
-
-typedef u32x4 g5x_u32x4_a4 __attribute__((aligned(4)));
-typedef uint32_t g5x_u32x2_t __attribute__((ext_vector_type(2)));
-typedef g5x_u32x2_t g5x_u32x2_a4 __attribute__((aligned(4)));
-typedef __attribute__((address_space(1))) const g5x_u32x4_a4 g5x_gx4;
-typedef __attribute__((address_space(1))) const g5x_u32x2_a4 g5x_gx2;
-typedef __attribute__((address_space(1))) const uint32_t g5x_gx1;
-
-template <int DW>
-struct PairX {
-    uint32_t w[DW];
-};
-
-template <int DW>
-__device__ __forceinline__ PairX<DW> load_pairx(const uint8_t *p) {
-    PairX<DW> v;
-    const u32x4 a = *(g5x_gx4 *)(p), b = *(g5x_gx4 *)(p + 16);
-    v.w[0] = a.x; v.w[1] = a.y; v.w[2] = a.z; v.w[3] = a.w;
-    v.w[4] = b.x; v.w[5] = b.y; v.w[6] = b.z; v.w[7] = b.w;
-    if constexpr (DW == 12) {
-        const u32x4 c = *(g5x_gx4 *)(p + 32);
-        v.w[8] = c.x; v.w[9] = c.y; v.w[10] = c.z; v.w[11] = c.w;
-    } else {
-        const g5x_u32x2_t c = *(g5x_gx2 *)(p + 32);
-        v.w[8] = c.x; v.w[9] = c.y;
-        if constexpr (DW == 11) v.w[10] = *(g5x_gx1 *)(p + 40);
-    }
-    return v;
-}
-
-// one block: the 32 values 0..15 / 0..31 as eight dwords in element order, fp16 d and m as f32
-struct BlockX {
-    uint32_t q[8];
-    float d, m;
-};
-
-template <bool QH>
-__device__ __forceinline__ void q5x_expand(BlockX &o, uint32_t s0, uint32_t s1, uint32_t s2, uint32_t s3, uint32_t qh) {
-    const uint32_t s[4] = {s0, s1, s2, s3};
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        o.q[i] = s[i] & 0x0F0F0F0Fu;
-        o.q[4 + i] = (s[i] >> 4) & 0x0F0F0F0Fu;
-        if (QH) {
-            o.q[i] |= q5x_spread4(qh, 4 * i);
-            o.q[4 + i] |= q5x_spread4(qh, 16 + 4 * i);
-        }
-    }
-}
-
-template <bool QH, bool MIN>
-__device__ __forceinline__ void q5x_decode_pair(const PairX<Q5x<QH, MIN>::DW> &v, BlockX &A, BlockX &B) {
-    const uint32_t *w = v.w;
-    if constexpr (!MIN) {                                   // Q5_0: 22-byte blocks
-        A.d = h2f(w[0] & 0xFFFFu);
-        B.d = h2f(w[5] >> 16);
-        A.m = B.m = 0.0f;
-        q5x_expand<true>(A, __builtin_amdgcn_alignbyte(w[2], w[1], 2), __builtin_amdgcn_alignbyte(w[3], w[2], 2),
-                         __builtin_amdgcn_alignbyte(w[4], w[3], 2), __builtin_amdgcn_alignbyte(w[5], w[4], 2),
-                         __builtin_amdgcn_alignbyte(w[1], w[0], 2));
-        q5x_expand<true>(B, w[7], w[8], w[9], w[10], w[6]);
-    } else if constexpr (QH) {                              // Q5_1: 24-byte blocks
-        A.d = h2f(w[0] & 0xFFFFu);
-        A.m = h2f(w[0] >> 16);
-        B.d = h2f(w[6] & 0xFFFFu);
-        B.m = h2f(w[6] >> 16);
-        q5x_expand<true>(A, w[2], w[3], w[4], w[5], w[1]);
-        q5x_expand<true>(B, w[8], w[9], w[10], w[11], w[7]);
-    } else {                                                // Q4_1: 20-byte blocks
-        A.d = h2f(w[0] & 0xFFFFu);
-        A.m = h2f(w[0] >> 16);
-        B.d = h2f(w[5] & 0xFFFFu);
-        B.m = h2f(w[5] >> 16);
-        q5x_expand<false>(A, w[1], w[2], w[3], w[4], 0u);
-        q5x_expand<false>(B, w[6], w[7], w[8], w[9], 0u);
-    }
-}
 
 __device__ __forceinline__ int q5x_dot(const BlockX &b, const u32x4 xl, const u32x4 xh) {
     int s = 0;

@@ -82,6 +82,7 @@ def _bind(L):
         "ggml_hip_debug_q5_0_auto_algo": ([i64, i64, i64], i32),
         "ggml_hip_debug_q5_1_auto_algo": ([i64, i64, i64], i32),
         "ggml_hip_debug_set_q5_0_gemm_min_n": ([i32], i32),
+        "ggml_hip_debug_set_q41_q51_gemm_min_n": ([i32], i32),
         "ggml_hip_debug_set_q5x_gemv_policy": ([i32, i32, i32], i32),
         "ggml_hip_reserve_workspace": ([i64, i64], i32),
         "ggml_hip_reserve_workspace_mm": ([i64, i64, i64], i32),
@@ -325,7 +326,8 @@ def dequantize_q5_1(wq_dev, K, M, w_dev, stream=None):
 
 def mul_mat_q4_1(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_off=0, x_off=0, y_off=0):
     """Q4_1 rows (20 * K / 32 bytes each, 4-byte aligned) x f32 [N][K] -> f32 y[n * ldy + m]; algo 0 auto (exact mode,
-    or K too long for the GEMV: 4; else 1), 1 GEMV (column tiles), 4 exact.  No GEMM: 2 is invalid."""
+    or K too long for the GEMV: 4; N from the Q4_1 / Q5_1 GEMM threshold, by default never: 7; else 1), 1 GEMV (column
+    tiles), 4 exact, 7 int8-MFMA GEMM on the weights in place.  2 is invalid."""
     _mul_mat_typed("mul_mat_q4_1", w_dev, K, M, x_dev, N, y_dev, algo, ldy, stream, w_off, x_off, y_off)
 
 

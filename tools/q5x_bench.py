@@ -18,7 +18,14 @@ the GEMM arm wins at every larger swept N; the file's `min_n` is the largest of 
 GGML_HIP_Q5_0_GEMM_MIN_N), null if the GEMM does not win on every shape at the largest N.  The two arms are checked
 against each other within 1e-3 of the largest |y| before they are timed.  Fails without a HIP device.
 
-    python tools/q5x_bench.py [--what decode|prefill|both] [--rounds 10] [--out-dir profiles]
+Prefill of the types with a minimum (profiles/q5x1_gemm.json; --what prefill1).  Q4_1 and Q5_1 on the same three
+shapes, N = 9 .. 512: algo 1 (GEMV tiles) against algo 7 (quantize_q8_1_soa + k_gemm_q5x1 on the weights in place; the
+quantizer launch is inside the timed arm), the same method.  Beside them, as the yardstick of what the int8 path
+reaches on the shape, Q5_0's algo 2 arm on a matrix of its own in the same interleaved rounds.  Per type and shape
+`min_n` as above; the file's `min_n` is the largest over both types and all shapes: the recommended value of
+GGML_HIP_Q41_Q51_GEMM_MIN_N (the library's default stays "never").
+
+    python tools/q5x_bench.py [--what decode|prefill|prefill1|both|all] [--rounds 10] [--out-dir profiles]
 """
 import argparse
 import json
@@ -34,6 +41,7 @@ import ggml_hip  # noqa: E402
 SHAPES = ((4096, 4096), (4096, 11008), (11008, 4096))          # (K, M)
 LAYER_MULT = (4, 2, 1)                                         # launches of each shape in one LLaMA-7B layer
 NS = (9, 16, 32, 64, 128)
+NS1 = (9, 16, 32, 64, 128, 256, 512)
 HBM_TBS = 8.0
 DB = ggml_hip.DeviceBuffer
 # arm -> (block bytes, fp16 fields at the block's start, the mul_mat)
@@ -168,9 +176,68 @@ def prefill(L, s, a):
             "timing": "warm HIP-graph replays, device events, arms interleaved, median over rounds"}
 
 
+def prefill1(L, s, a):
+    rng = np.random.default_rng(0x51F)
+    nmax = max(NS1)
+    types = {name: [] for name in ("q4_1", "q5_1")}
+    for K, M in SHAPES:
+        x = rng.standard_normal((nmax, K)).astype(np.float32)
+        xd = DB.from_array(x)
+        ggml_hip.check(L.ggml_hip_reserve_workspace_mm(K, nmax, M))
+        w50 = DB.from_array(random_blocks(rng, M * (K // 32), 22, 1))
+        y50 = DB(nmax * M * 4)
+        for name in types:
+            bsize, nhalf, mm = ARMS[name]
+            wd = DB.from_array(random_blocks(rng, M * (K // 32), bsize, nhalf))
+            yd = {arm: DB(nmax * M * 4) for arm in ("gemv", "gemm")}
+            sweep = []
+            for N in NS1:
+                calls = {"gemv": lambda: mm(wd, K, M, xd, N, yd["gemv"], algo=1, stream=s),
+                         "gemm": lambda: mm(wd, K, M, xd, N, yd["gemm"], algo=7, stream=s),
+                         "q5_0_gemm8": lambda: ggml_hip.mul_mat_q5_0(w50, K, M, xd, N, y50, algo=2, stream=s)}
+                graphs, per_graph = {}, {}
+                for arm, fn in calls.items():
+                    fn()
+                    ggml_hip.check(L.ggml_hip_stream_synchronize(s))
+                    g = ggml_hip.Graph(s)
+                    with g:
+                        for _ in range(a.launches):
+                            fn()
+                    graphs[arm], per_graph[arm] = g, a.launches
+                ggml_hip.check(L.ggml_hip_stream_synchronize(s))
+                y1, y7 = yd["gemv"].download((N, M), np.float32), yd["gemm"].download((N, M), np.float32)
+                if not np.abs(y1 - y7).max() <= 1e-3 * np.abs(y1).max():
+                    sys.exit(f"q5x_bench prefill1: algo 7 differs from algo 1 on {name} at K = {K}, M = {M}, N = {N}")
+                us = timed_rounds(L, s, graphs, a.rounds, a.settle_ms, per_graph, "q5x_bench prefill1")
+                row = {"N": N}
+                for arm in calls:
+                    st = stats(us[arm])
+                    row.update({f"{arm}_{k}": v for k, v in st.items()})
+                row["gemm_TOPs"] = round(2.0 * M * K * N / row["gemm_us"] * 1e-6, 1)
+                row["gemv_over_gemm"] = round(row["gemv_us"] / row["gemm_us"], 3)
+                row["gemm_over_q5_0_gemm8"] = round(row["gemm_us"] / row["q5_0_gemm8_us"], 3)
+                sweep.append(row)
+            min_n = None
+            for row in reversed(sweep):
+                if row["gemv_over_gemm"] <= 1.0:
+                    break
+                min_n = row["N"]
+            types[name].append({"K": K, "M": M, "weight_bytes": M * (K // 32) * bsize, "sweep": sweep, "min_n": min_n})
+            del wd, yd
+        del xd, w50, y50
+    per_shape = [sh["min_n"] for shapes in types.values() for sh in shapes]
+    return {"bench": "q5x1_gemm", "launches_per_graph": a.launches, "rounds": a.rounds, "settle_ms": a.settle_ms,
+            "types": types, "min_n": None if None in per_shape else max(per_shape),
+            "min_n_note": "the smallest swept N from which algo 7 wins on every shape of both types at every larger "
+                          "swept N: the recommended GGML_HIP_Q41_Q51_GEMM_MIN_N (the default is never)",
+            "gemm_arm": "quantize_q8_1_soa + k_gemm_q5x1 (weights read in place)",
+            "q5_0_gemm8_arm": "Q5_0, same shape: gemm8_prep_x + k_prep8_w_q5_0 (weight image per call) + k_gemm8",
+            "timing": "warm HIP-graph replays, device events, arms interleaved, median over rounds"}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", choices=("decode", "prefill", "both"), default="both")
+    ap.add_argument("--what", choices=("decode", "prefill", "prefill1", "both", "all"), default="both")
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--launches", type=int, default=10)
     ap.add_argument("--settle-ms", type=float, default=40.0)
@@ -183,8 +250,9 @@ def main():
     ggml_hip.check(L.ggml_hip_set_device(0))
     ggml_hip.check(L.ggml_hip_set_exact(0))
     s = L.ggml_hip_default_stream()
-    for what, fn, out in (("decode", decode, "q5x_gemv.json"), ("prefill", prefill, "q5x_gemm.json")):
-        if a.what not in (what, "both"):
+    for what, fn, out in (("decode", decode, "q5x_gemv.json"), ("prefill", prefill, "q5x_gemm.json"),
+                          ("prefill1", prefill1, "q5x1_gemm.json")):
+        if a.what not in (what, "all") and not (a.what == "both" and what != "prefill1"):
             continue
         line = json.dumps(fn(L, s, a))
         print(line, flush=True)
