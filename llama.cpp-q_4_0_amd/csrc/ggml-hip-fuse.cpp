@@ -200,10 +200,14 @@ bool dev_f32(const tensor *t) {
     return t && t->backend == gabi::BACKEND_GPU && t->type == gabi::TYPE_F32 && t->extra && is_contiguous(t);
 }
 bool host_scalar_param(const tensor *t) { return t && t->backend == gabi::BACKEND_CPU && t->data; }
-bool overlaps(const tensor *a, const tensor *b) {   // device byte ranges of two device tensors
+// device byte ranges of two device tensors, strides included: a strided view (a cache window, a permute)
+// reaches past its first nbytes, and a rope -> cpy into such a target that lay on the rope's input was fused
+// when this compared nbytes (tests/test_gpu_sched_hazards.py, rope_cpy_strided_span)
+size_t span_bytes(const tensor *t);
+bool overlaps(const tensor *a, const tensor *b) {
     if (!a || !b || a->backend != gabi::BACKEND_GPU || b->backend != gabi::BACKEND_GPU || !a->extra || !b->extra) return false;
     const char *pa = dptr(a), *pb = dptr(b);
-    return pa < pb + gabi::nbytes(b) && pb < pa + gabi::nbytes(a);
+    return pa < pb + span_bytes(b) && pb < pa + span_bytes(a);
 }
 
 bool deferrable(const tensor *t) {
@@ -378,26 +382,46 @@ bool try_fuse(tensor *t) {
         const tensor *m = t->src0, *cb = t->src1;
         if (m->ne[0] == last->ne[0] && m->ne[1] == last->ne[2] && m->ne[2] == last->ne[1] && m->ne[3] == 1 &&
             m->nb[0] == 4 && m->nb[1] == last->nb[2] && m->nb[2] == last->nb[1] && dev_f32(cb) &&
-            gabi::nbytes(cb) == gabi::nbytes(last) && !overlaps(cb, last) && !overlaps(cb, last->src0) &&
-            !overlaps(cb, p.node[2]) && !overlaps(cb, p.node[0]->src0)) {
-            const tensor *sc = p.node[0], *mk = p.node[1], *sm = p.node[2], *kqv = last, *vv = kqv->src0;
-            const char *kq = dptr(sc->src0);
-            // stores into the buffer the workgroups read (the in-place chain) are skipped: see
-            // k_softmax_kqv; no node reads them, KQV consumes the softmax inside the launch
-            auto out = [&](const tensor *x) { return overlaps(x, sc->src0) ? nullptr : (float *)dptr(x); };
+            gabi::nbytes(cb) == gabi::nbytes(last)) {
+            const tensor *sc = p.node[0], *mk = p.node[1], *sm = p.node[2], *kqv = last, *vv = kqv->src0, *kqt = sc->src0;
+            tensor *kqn = g_kq && same_tensor(kqt, g_kq) ? g_kq : nullptr;     // KQ still held: K and q still unread
+            const tensor *chain[4] = {kqn, sc, mk, sm};
+            // The launch's workgroups read and store side by side, so what KQV and the merge copy store must lie on
+            // nothing else the launch reads or stores.  In ggml's order those tensors are dead by then, and a scratch
+            // ring that wraps does place new outputs on them (tests/test_gpu_sched_hazards.py, attn_*).
+            bool clash = overlaps(cb, kqv);
+            for (const tensor *o : {kqv, cb})
+                for (const tensor *x : {kqt, sc, mk, sm, vv})
+                    if (overlaps(o, x)) clash = true;
+            // KQ in the same launch: also nothing it stores may lie on K or q (else KQ runs first, as its own launch)
+            bool fold = kqn && kq_chain_ok(kqn, sm);
+            if (fold)
+                for (const tensor *o : {(const tensor *)kqn, sc, mk, sm, kqv, cb})
+                    if (overlaps(o, kqn->src0) || overlaps(o, kqn->src1)) fold = false;
+            // every buffer of the chain is stored once, by the last tensor of the chain that owns it (in-place
+            // scale / mask / soft_max)
+            float *st[4];
+            for (int i = 0; i < 4; i++) {
+                st[i] = chain[i] ? (float *)dptr(chain[i]) : nullptr;
+                for (int k = i + 1; k < 4; k++)
+                    if (dev_overlap(chain[i], chain[k])) st[i] = nullptr;
+            }
+            // KQ from its own launch and a chain in place on it: one workgroup would store the chain's values over
+            // the kq the others still read, so they read kq from the stream workspace instead: KQ's launch writes
+            // there when it is still held and the scale overwrites its whole buffer, else kq is copied there
+            const float *kq = (const float *)dptr(kqt);
+            bool to_ws = false;
+            for (int i = 1; i < 4 && !fold; i++)
+                if (st[i] && overlaps(chain[i], kqt)) to_ws = true;
+            void *ws = nullptr;
+            // (kq grows by a row element per token and the workspace grows to exactly what is asked, with a device
+            // synchronize: ask in steps of 1 MiB)
+            const size_t ws_need = (gabi::nbytes(kqt) + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
+            if (!clash && to_ws && stream_workspace(id, s, ws_need, &ws) != GGML_HIP_OK) clash = true;
+            if (clash) return false;                 // (nothing launched: the caller runs the nodes one by one)
             const OpTables &tb = op_tables(id, s);
             HIP_FATAL(hipSetDevice(id));
-            tensor *kqn = g_kq;
-            if (kqn && same_tensor(sc->src0, kqn) && kq_chain_ok(kqn, sm)) {
-                // KQ in the same launch: no workgroup reads kq from memory, so every buffer of the chain is
-                // stored once, by the last tensor of the chain that owns it (in-place scale / mask / soft_max)
-                const tensor *chain[4] = {kqn, sc, mk, sm};
-                float *st[4];
-                for (int i = 0; i < 4; i++) {
-                    st[i] = (float *)dptr(chain[i]);
-                    for (int k = i + 1; k < 4; k++)
-                        if (dev_overlap(chain[i], chain[k])) st[i] = nullptr;
-                }
+            if (fold) {
                 const tensor *K = kqn->src0, *Q = kqn->src1;
                 g_kq = nullptr;
                 HIP_FATAL(ghip::op_kq_softmax_kqv(dptr(K), K->nb[1], K->nb[2], (const float *)dptr(Q), Q->nb[2], (int)K->ne[0],
@@ -407,8 +431,22 @@ bool try_fuse(tensor *t) {
                 count_node(kqn);
                 g_fused[14].fetch_add(1, std::memory_order_relaxed);
             } else {
-                flush_kq();
-                HIP_FATAL(ghip::op_softmax_kqv((const float *)kq, out(sc), out(mk), out(sm), *(const float *)sc->src1->data,
+                if (to_ws && kqn && dptr(sc) == dptr(kqn) && gabi::nbytes(sc) == gabi::nbytes(kqn)) {
+                    tensor tmp = *kqn;               // KQ's own launch, into the workspace
+                    ggml_tensor_extra_gpu ex{};
+                    ex.data_device[id] = ws;
+                    tmp.extra = &ex;
+                    g_kq = nullptr;
+                    run_device_op(&tmp);
+                } else {
+                    flush_kq();
+                    if (to_ws)
+                        HIP_FATAL(ghip::op_cpy_f32(kq, (char *)ws, false, kqt->ne[0] * kqt->ne[1] * kqt->ne[2], kqt->ne[0], kqt->ne[1],
+                                                   kqt->nb[0], kqt->nb[1], kqt->nb[2], kqt->ne[0], kqt->ne[1], kqt->nb[0],
+                                                   kqt->nb[1], kqt->nb[2], s));
+                }
+                if (to_ws) kq = (const float *)ws;
+                HIP_FATAL(ghip::op_softmax_kqv(kq, st[1], st[2], st[3], *(const float *)sc->src1->data,
                                                ((const int32_t *)mk->src1->data)[0], tb.exp, sm->ne[0], sm->ne[2], dptr(vv),
                                                vv->nb[1], vv->nb[2], vv->ne[1], (float *)dptr(kqv), (float *)dptr(cb), s));
             }
@@ -526,11 +564,7 @@ size_t span_bytes(const tensor *t) {
     for (int i = 0; i < 4; i++) last += (size_t)(t->ne[i] - 1) * t->nb[i];
     return last;
 }
-bool dev_overlap(const tensor *a, const tensor *b) {
-    if (!a || !b || a->backend != gabi::BACKEND_GPU || b->backend != gabi::BACKEND_GPU || !a->extra || !b->extra) return false;
-    const char *pa = dptr(a), *pb = dptr(b);
-    return pa < pb + span_bytes(b) && pb < pa + span_bytes(a);
-}
+bool dev_overlap(const tensor *a, const tensor *b) { return overlaps(a, b); }
 
 bool main_device_only_split(int64_t M) {
     int active = 0, only = -1;

@@ -140,3 +140,164 @@ class Nodes:
         for t in reversed(self.owned):
             self.L.ggml_hip_free_data(ctypes.byref(t))
         self.owned = []
+        if self.ring_size:
+            self.L.ggml_hip_free_scratch()
+            self.L.ggml_hip_set_scratch_size(0)          # the process default
+            self.ring_size = 0
+
+    # ---- placement in the VRAM scratch ring, by the product's own mechanism (ggml_hip_assign_buffers)
+    ring_size = 0
+
+    def ring_begin(self, size):
+        """a fresh ring of `size` bytes: the next assignment lands at offset 0.  (set_scratch_size does not
+        reallocate, so the old ring is freed first.)"""
+        L = self.L
+        L.ggml_hip_set_scratch_size.argtypes = [ctypes.c_size_t]
+        L.ggml_hip_set_scratch_size.restype = None
+        L.ggml_hip_free_scratch()
+        L.ggml_hip_set_scratch_size(size)
+        self.ring_size, self.ring_off = size, 0
+        self.ring_gran = 65536                           # assign_buffers_impl's slot rule
+        while self.ring_gran > 256 and self.ring_gran > size // 2048:
+            self.ring_gran >>= 1
+        probe = self._filler(0)                          # an empty tensor: allocates the ring, moves nothing
+        self.ring_base = self.dev_ptr(probe)
+
+    def dev_ptr(self, t):
+        return ctypes.cast(t.extra, ctypes.POINTER(ctypes.c_void_p * 16)).contents[0]
+
+    def _assign(self, t):
+        """ggml_hip_assign_buffers(t), and where assign_buffers_impl's ring rule puts a tensor of its size"""
+        size = int(np.prod([t.ne[i] for i in range(4)])) * ES[t.type]
+        if self.ring_off + size > self.ring_size:
+            self.ring_off = 0
+        at = self.ring_off
+        self.ring_off += (size + self.ring_gran - 1) & ~(self.ring_gran - 1)
+        self.L.ggml_hip_assign_buffers(ctypes.byref(t))
+        assert t.backend == ggml_hip.GGML_BACKEND_GPU and t.extra
+        self.keep.append(t)
+        self.owned.append(t)                             # (free_data only forgets the extra of a ring tensor)
+        return at
+
+    def _filler(self, nbytes):
+        assert nbytes % 4 == 0
+        t = _tensor(TYPE_F32, [nbytes // 4])
+        t.ne[0] = nbytes // 4
+        self._assign(t)
+        return t
+
+    def ring_place(self, t, off):
+        """assign t (not in place, not a CPY) to the ring at byte `off`, steering there with throw-away filler
+        assignments and the ring's wrap; asserts the device offset"""
+        size = int(np.prod([t.ne[i] for i in range(4)])) * ES[t.type]
+        assert off % self.ring_gran == 0 and off + size <= self.ring_size
+        if self.ring_off > off:                          # run to the end: the next assignment wraps to 0
+            if self.ring_off < self.ring_size:
+                self._filler(self.ring_size - self.ring_off)
+            self.ring_off = 0                            # (where the next non-empty assignment goes)
+        if self.ring_off < off:
+            self._filler(off - self.ring_off)
+        assert self.ring_off == off, (self.ring_off, off)
+        at = self._assign(t)
+        assert at == off and self.dev_ptr(t) - self.ring_base == off, (at, off, self.dev_ptr(t) - self.ring_base)
+        return t
+
+    def blank(self, gtype, ne, nb=None, op=0):
+        """a tensor struct with host data of its own (assign_buffers tells in-place nodes by equal data pointers)"""
+        t = _tensor(gtype, ne, nb)
+        t.op = op
+        buf = np.zeros(8, np.uint8)
+        t.data = buf.ctypes.data
+        self.keep += [buf, t]
+        return t
+
+    def at(self, ptr, gtype, ne, nb=None, op=0, src0=None):
+        """a device tensor (or view: reshape, cache window, PERMUTE with op and src0) at device address ptr"""
+        t = self.blank(gtype, ne, nb, op)
+        extra = (ctypes.c_void_p * 16)()
+        extra[0] = ptr
+        t.backend, t.extra = ggml_hip.GGML_BACKEND_GPU, ctypes.addressof(extra)
+        if src0 is not None:
+            t.src0 = ctypes.pointer(src0)
+        self.keep.append(extra)
+        return t
+
+    def permute(self, src0, ne, nb):
+        """a PERMUTE view of src0 with the given extents and strides"""
+        return self.at(self.dev_ptr(src0), src0.type, ne, nb, _OPS["PERMUTE"], src0)
+
+    def weight_q4_0(self, wq, k, m):
+        """a resident q4_0 weight [m rows of k] (transform_tensor, BACKEND_GPU)"""
+        wq = np.ascontiguousarray(wq, np.uint8)
+        t = ggml_hip.make_tensor(ggml_hip.GGML_TYPE_Q4_0, (k, m), wq, backend=ggml_hip.GGML_BACKEND_GPU)
+        self.L.ggml_hip_transform_tensor(wq.ctypes.data_as(ctypes.c_void_p), ctypes.byref(t))
+        assert t.backend == ggml_hip.GGML_BACKEND_GPU and t.extra
+        self.keep += [wq, t]
+        self.owned.append(t)
+        return t
+
+    def op_tensor(self, op, ne, src0, src1=None, inplace=False):
+        """an F32 node struct of extents ne, not yet placed; inplace: its data is src0's, as ggml's _inplace ops"""
+        t = self.blank(TYPE_F32, ne, op=op)
+        t.src0 = ctypes.pointer(src0)
+        if src1 is not None:
+            t.src1 = ctypes.pointer(src1)
+        if inplace:
+            t.data = src0.data
+        return t
+
+    def mm_q4_0(self, w, x):
+        """a q4_0 MUL_MAT node struct (device x, device y once placed)"""
+        return self.op_tensor(OP_MUL_MAT, [w.ne[1], x.ne[1]], w, x)
+
+    def assign_inplace(self, t):
+        """ggml_hip_assign_buffers of an in-place node: it takes its src0's device address"""
+        want = self.dev_ptr(t.src0.contents)
+        off = self.ring_off
+        self.L.ggml_hip_assign_buffers(ctypes.byref(t))
+        self.ring_off = off
+        assert t.extra and self.dev_ptr(t) == want
+        self.keep.append(t)
+        self.owned.append(t)
+        return t
+
+    def upload(self, ptr, arr):
+        arr = np.ascontiguousarray(arr)
+        ggml_hip.check(self.L.ggml_hip_memcpy_h2d(ctypes.c_void_p(ptr), arr.ctypes.data_as(ctypes.c_void_p), arr.nbytes, None), "h2d")
+
+    def download(self, ptr, nbytes):
+        """device bytes (the read flushes what the scheduler holds)"""
+        out = np.empty(nbytes, np.uint8)
+        ggml_hip.check(self.L.ggml_hip_memcpy_d2h(out.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(ptr), nbytes, None), "d2h")
+        return out
+
+
+def _env_switch(name):
+    v = os.environ.get(name)
+    return 1 if v is None else (0 if not re.match(r"\s*[+-]?0*[1-9]", v) else 1)
+
+
+class restore_switches:
+    """with restore_switches(L): ... puts back the exact mode (its getter's value) and the fusion and fold switches
+    (no getters: the defaults their environment variables give) on the way out"""
+
+    def __init__(self, L):
+        self.L = L
+
+    def __enter__(self):
+        self.exact = self.L.ggml_hip_get_exact()
+        return self
+
+    def __exit__(self, *exc):
+        L = self.L
+        L.ggml_hip_set_exact(self.exact)
+        set_fuse(L, FUSE_DEFAULT)
+        nf = os.environ.get("GGML_HIP_NORM_FOLD")
+        nf = int(nf) if nf is not None and re.fullmatch(r"\s*[012]\s*", nf) else 1
+        for fn, v in (("ggml_hip_debug_set_norm_fold", nf), ("ggml_hip_debug_set_epi_fold", _env_switch("GGML_HIP_GEMV_EPI")),
+                      ("ggml_hip_debug_set_kq_fold", _env_switch("GGML_HIP_KQ_FOLD")),
+                      ("ggml_hip_debug_set_x9_fold", _env_switch("GGML_HIP_X9_FOLD"))):
+            f = getattr(L, fn)
+            f.argtypes = [ctypes.c_int]
+            f(v)
+        return False
