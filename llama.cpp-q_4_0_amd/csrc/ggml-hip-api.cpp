@@ -100,7 +100,7 @@ int ggml_hip_debug_q8_0_auto_algo(int64_t K, int64_t M, int64_t N) { return debu
 
 int ggml_hip_debug_set_q8_0_gemm_min_n(int n) { return weight_type(gabi::TYPE_Q8_0)->min_n->set(n); }
 
-// Q4_1 / Q5_0 / Q5_1 (q5x_w.hip)
+// Q4_1 / Q5_0 / Q5_1 (blk32_w.hip)
 static int dequantize_q5x(int type, const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
     if (const int rc = check_dequantize(type, dev_wq, K, M, dev_w); rc != GGML_HIP_OK) return rc;
     HIP_RET(ghip::dequantize_q5x(type != gabi::TYPE_Q4_1, type != gabi::TYPE_Q5_0, dev_wq, K, M, dev_w,
@@ -221,8 +221,9 @@ int ggml_hip_mul_mat_q4_0_multi(int n, const void *const *dev_w, const int64_t *
         void *ws = nullptr;
         const int wrc = stream_workspace(id, s, workspace_bytes(K, N), &ws);
         if (wrc != GGML_HIP_OK) return wrc;
-        int8_t *qs = (int8_t *)ws;
-        float *xd = (float *)((char *)ws + ((size_t)(N * K + 255) & ~(size_t)255));
+        const XPlanes xp = x_planes(ws, K, N);
+        int8_t *qs = xp.qs;
+        float *xd = xp.d;
         HIP_RET(ghip::quantize_q8_0_soa(dev_x, K, N, qs, xd, s));
         int64_t ldy[ghip::GEMV_MULTI_MAX];
         for (int i = 0; i < n; i++) ldy[i] = M[i];

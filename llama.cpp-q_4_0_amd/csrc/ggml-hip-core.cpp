@@ -117,11 +117,16 @@ void pool_free(int id, void *p, size_t size) {
     d.pool.push_back({p, size});
 }
 
-// workspace for the q8_0 activations of one mul_mat: qs [N][K] int8 + d [N][K/32] f32 + the same d as
-// fp16, block-major [K/32][N rounded up to 4] (the LDS GEMM's operand layout)
-size_t ws_d16_offset(int64_t K, int64_t N) {
-    const size_t qs = (size_t)(N * K + 255) & ~(size_t)255;
-    return qs + (((size_t)N * (K / QK) * 4 + 255) & ~(size_t)255);
+// the planes of a quantized x at the start of a workspace: qs [N][K] int8, d [N][K/32] f32, and behind them a third
+// plane (q8_1's s [N][K/32] f32, or the fp16 copy of d below); every plane starts at a multiple of 256 bytes
+static size_t pad256(size_t n) { return (n + 255) & ~(size_t)255; }
+static size_t ws_d_offset(int64_t K, int64_t N) { return pad256((size_t)(N * K)); }
+static size_t ws_d_bytes(int64_t K, int64_t N) { return pad256((size_t)N * (K / QK) * 4); }
+// workspace for the q8_0 activations of one mul_mat: the qs and d planes + the same d as fp16, block-major
+// [K/32][N rounded up to 4] (the LDS GEMM's operand layout), in the third plane's place
+size_t ws_d16_offset(int64_t K, int64_t N) { return ws_d_offset(K, N) + ws_d_bytes(K, N); }
+XPlanes x_planes(void *ws, int64_t K, int64_t N) {
+    return {(int8_t *)ws, (float *)((char *)ws + ws_d_offset(K, N)), (float *)((char *)ws + ws_d16_offset(K, N))};
 }
 size_t workspace_bytes(int64_t K, int64_t N) { return ws_d16_offset(K, N) + (size_t)((N + 3) & ~3) * (K / QK) * 2; }
 // the LDS GEMM (algo 2, v8 / v9) adds its x image and the per-call weight image of an M-row matrix (room
@@ -278,9 +283,10 @@ int mul_mat_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, 
     }
     const int wrc = stream_workspace(id, s, workspace_bytes(K, N), &ws);
     if (wrc != GGML_HIP_OK) return wrc;
-    int8_t *qs = (int8_t *)ws;
-    float *xd = (float *)((char *)ws + ((size_t)(N * K + 255) & ~(size_t)255));
-    uint16_t *xd16 = (uint16_t *)((char *)ws + ws_d16_offset(K, N));
+    const XPlanes xp = x_planes(ws, K, N);
+    int8_t *qs = xp.qs;
+    float *xd = xp.d;
+    uint16_t *xd16 = (uint16_t *)xp.s;                       // the fp16 d copy takes the third plane's place
     // the fp16 block-major d_x copy (gemm7) is written whenever qs/d are: a sibling group may mix algos
     if (!(*xq & XQ_SOA)) HIP_RET(ghip::quantize_q8_0_soa(x, K, N, qs, xd, s, xd16));
     *xq |= XQ_SOA;
@@ -379,7 +385,7 @@ static const WeightType ROW_Q4_K = {
     ERR_K256, ERR_ALIGN_Q45K, ERR_GEMV_Q45K,
     QK_K, 16, ERR_DQ_Q45K};
 
-// Q4_1 / Q5_0 / Q5_1 (q5x_w.hip).  Q5_0's values q - 16 are int8 and its activations q8_0, so it takes Q8_0's GEMM
+// Q4_1 / Q5_0 / Q5_1 (blk32_w.hip).  Q5_0's values q - 16 are int8 and its activations q8_0, so it takes Q8_0's GEMM
 // (algo 2).  Q4_1 and Q5_1 cannot: their activation scale is an unrounded f32 and they carry a second term m_w s_x
 // per block, which k_gemm8's fp16 d_x plane and single-term epilogue do not hold.  They have a GEMM of their own on
 // the weights in place (algo 7, k_gemm_q5x1) behind a threshold of their own whose default is "never": until it is
@@ -442,7 +448,7 @@ int check_operands(const WeightType &t, const void *w, int64_t K, int64_t M, con
 // against the 288 of workspace_bytes(K, N) behind the same padding of qs.  None is more than workspace_bytes(K, N),
 // which ggml_hip_reserve_workspace reserves.
 static size_t workspace_bytes_q8k(int64_t K, int64_t N) { return (size_t)N * (size_t)(K / QK_K) * Q8KB; }
-static size_t kquant_planes_offset(int64_t K, int64_t N) { return (size_t)(N * K + 255) & ~(size_t)255; }
+static size_t kquant_planes_offset(int64_t K, int64_t N) { return ws_d_offset(K, N); }
 static size_t workspace_bytes_q6k_gemm(int64_t K, int64_t N) {
     return kquant_planes_offset(K, N) + (size_t)N * (size_t)(K / QK_K) * 4;
 }
@@ -490,59 +496,27 @@ static int mul_mat_q6k_dev(const void *w, int64_t K, int64_t M, const float *x, 
     return GGML_HIP_OK;
 }
 
-// Q8_0 weights (q8_0_w.hip): algo 2 = the weight's k_gemm8 image built per call into the workspace (k_prep8_w_q8_0;
-// the way GEMM version 9 treats an unregistered q4_0 weight; ggml_hip_reserve_workspace_mm budgets its 34 B per 32
-// weights), then gemm8_prep_x + gemm8_run unchanged; algo 4 = the SoA q8_0 quantizer + the exact kernel
-static int mul_mat_q8_0_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
-                            hipStream_t s) {
-    const int rc = check_operands(ROW_Q8_0, w, K, M, x, N, y, ldy);
-    if (rc != GGML_HIP_OK || N == 0) return rc;
-    const int id = current_device();
-    if (algo == 0) algo = auto_algo(ROW_Q8_0, K, N);
-    if (algo == 1) {
-        if (!ROW_Q8_0.gemv_takes_k(K)) return fail(GGML_HIP_ERR_UNSUPPORTED, ROW_Q8_0.err_gemv_k);
-        HIP_RET(ghip::gemv_q8_0w(w, K, M, x, N, y, ldy, g_dev[id].info, s));
-        return GGML_HIP_OK;
-    }
-    if (algo != 2 && algo != 4) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1, 2 or 4");
-    void *ws = nullptr;
-    if (algo == 2) {
-        if ((N + 7) / 8 > 65535) return fail(GGML_HIP_ERR_UNSUPPORTED, "too many columns for one launch; split columns");
-        const int wrc = stream_workspace(id, s, workspace_bytes_mm(K, N, M), &ws);
-        if (wrc != GGML_HIP_OK) return wrc;
-        void *xws = (char *)ws + ws_g8x_offset(K, N), *wws = (char *)ws + ws_g8w_offset(K, N);
-        HIP_RET(ghip::gemm8_prep_x(x, K, N, xws, s));
-        HIP_RET(ghip::gemm8_prep_w_q8_0(w, K, M, wws, s));
-        HIP_RET(ghip::gemm8_run(wws, K, M, xws, N, y, ldy, s));
-        return GGML_HIP_OK;
-    }
-    const int wrc = stream_workspace(id, s, workspace_bytes(K, N), &ws);
-    if (wrc != GGML_HIP_OK) return wrc;
-    int8_t *qs = (int8_t *)ws;
-    float *xd = (float *)((char *)ws + ((size_t)(N * K + 255) & ~(size_t)255));
-    HIP_RET(ghip::quantize_q8_0_soa(x, K, N, qs, xd, s));
-    HIP_RET(ghip::mm_exact_q8_0w(w, K, M, qs, xd, N, y, ldy, s));
-    return GGML_HIP_OK;
-}
-
-// Q4_1 / Q5_0 / Q5_1 (q5x_w.hip): algo 2 (Q5_0 only) = the k_gemm8 image of q - 16 built per call into the workspace
-// (k_prep8_w_q5_0), then gemm8_prep_x + gemm8_run unchanged, as Q8_0; algo 4 = the SoA quantizer (q8_0's planes for
-// Q5_0; q8_1's qs, d and s for the types with a minimum, workspace_bytes_q81) + the exact kernel; algo 7 (the types
-// with a minimum only, any N >= 1, no K limit) = the same q8_1 planes + k_gemm_q5x1 on the weights in place
-// (q5x_gemm.hip)
-size_t workspace_bytes_q81(int64_t K, int64_t N) {
-    const size_t plane = ((size_t)N * (K / QK) * 4 + 255) & ~(size_t)255;
-    return (((size_t)(N * K) + 255) & ~(size_t)255) + 2 * plane;
-}
-static int mul_mat_q5x_dev(const WeightType &t, bool qh, bool mn, const void *w, int64_t K, int64_t M, const float *x,
-                           int64_t N, float *y, int64_t ldy, int algo, hipStream_t s) {
+// Q8_0 / Q4_1 / Q5_0 / Q5_1 (blk32_w.hip), one body over the four rows.  mn: the type has a minimum and q8_1
+// activations (Q4_1, Q5_1); the other two multiply against q8_0.  algo 2 (Q8_0 and Q5_0) = the weight's k_gemm8 image
+// built per call into the workspace (k_prep8_w: the int8 weights verbatim, or q - 16; the way GEMM version 9 treats
+// an unregistered q4_0 weight; ggml_hip_reserve_workspace_mm budgets its 34 B per 32 weights), then gemm8_prep_x +
+// gemm8_run unchanged; algo 4 = the SoA quantizer (q8_0's planes; q8_1's qs, d and s for the types with a minimum,
+// workspace_bytes_q81) + the exact kernel; algo 7 (the types with a minimum only, any N >= 1, no K limit) = the same
+// q8_1 planes + k_gemm_q5x1 on the weights in place (q5x_gemm.hip)
+size_t workspace_bytes_q81(int64_t K, int64_t N) { return ws_d16_offset(K, N) + ws_d_bytes(K, N); }
+enum class Blk32 { Q8_0, Q4_1, Q5_0, Q5_1 };
+static int mul_mat_blk32_dev(const WeightType &t, Blk32 type, const void *w, int64_t K, int64_t M, const float *x, int64_t N,
+                             float *y, int64_t ldy, int algo, hipStream_t s) {
+    const bool q8 = type == Blk32::Q8_0, mn = type == Blk32::Q4_1 || type == Blk32::Q5_1;
+    const bool qh = type == Blk32::Q5_0 || type == Blk32::Q5_1;
     const int rc = check_operands(t, w, K, M, x, N, y, ldy);
     if (rc != GGML_HIP_OK || N == 0) return rc;
     const int id = current_device();
     if (algo == 0) algo = auto_algo(t, K, N);
     if (algo == 1) {
         if (!t.gemv_takes_k(K)) return fail(GGML_HIP_ERR_UNSUPPORTED, t.err_gemv_k);
-        HIP_RET(ghip::gemv_q5x(qh, mn, w, K, M, x, N, y, ldy, g_dev[id].info, s));
+        HIP_RET(q8 ? ghip::gemv_q8_0w(w, K, M, x, N, y, ldy, g_dev[id].info, s)
+                   : ghip::gemv_q5x(qh, mn, w, K, M, x, N, y, ldy, g_dev[id].info, s));
         return GGML_HIP_OK;
     }
     if (algo != 4 && algo != (mn ? 7 : 2))
@@ -555,36 +529,40 @@ static int mul_mat_q5x_dev(const WeightType &t, bool qh, bool mn, const void *w,
         if (wrc != GGML_HIP_OK) return wrc;
         void *xws = (char *)ws + ws_g8x_offset(K, N), *wws = (char *)ws + ws_g8w_offset(K, N);
         HIP_RET(ghip::gemm8_prep_x(x, K, N, xws, s));
-        HIP_RET(ghip::gemm8_prep_w_q5_0(w, K, M, wws, s));
+        HIP_RET(q8 ? ghip::gemm8_prep_w_q8_0(w, K, M, wws, s) : ghip::gemm8_prep_w_q5_0(w, K, M, wws, s));
         HIP_RET(ghip::gemm8_run(wws, K, M, xws, N, y, ldy, s));
         return GGML_HIP_OK;
     }
     const int wrc = stream_workspace(id, s, mn ? workspace_bytes_q81(K, N) : workspace_bytes(K, N), &ws);
     if (wrc != GGML_HIP_OK) return wrc;
-    int8_t *qs = (int8_t *)ws;
-    float *xd = (float *)((char *)ws + ((size_t)(N * K + 255) & ~(size_t)255));
-    float *xs = (float *)((char *)xd + (((size_t)N * (K / QK) * 4 + 255) & ~(size_t)255));
+    const XPlanes xp = x_planes(ws, K, N);
     if (mn)
-        HIP_RET(ghip::quantize_q8_1_soa(x, K, N, qs, xd, xs, s));
+        HIP_RET(ghip::quantize_q8_1_soa(x, K, N, xp.qs, xp.d, xp.s, s));
     else
-        HIP_RET(ghip::quantize_q8_0_soa(x, K, N, qs, xd, s));
+        HIP_RET(ghip::quantize_q8_0_soa(x, K, N, xp.qs, xp.d, s));
     if (algo == 7)
-        HIP_RET(ghip::gemm_q5x1(qh, w, K, M, qs, xd, xs, N, y, ldy, g_dev[id].info, s));
+        HIP_RET(ghip::gemm_q5x1(qh, w, K, M, xp.qs, xp.d, xp.s, N, y, ldy, g_dev[id].info, s));
+    else if (q8)
+        HIP_RET(ghip::mm_exact_q8_0w(w, K, M, xp.qs, xp.d, N, y, ldy, s));
     else
-        HIP_RET(ghip::mm_exact_q5x(qh, mn, w, K, M, qs, xd, xs, N, y, ldy, s));
+        HIP_RET(ghip::mm_exact_q5x(qh, mn, w, K, M, xp.qs, xp.d, xp.s, N, y, ldy, s));
     return GGML_HIP_OK;
+}
+static int mul_mat_q8_0_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                            hipStream_t s) {
+    return mul_mat_blk32_dev(ROW_Q8_0, Blk32::Q8_0, w, K, M, x, N, y, ldy, algo, s);
 }
 static int mul_mat_q4_1_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
                             hipStream_t s) {
-    return mul_mat_q5x_dev(ROW_Q4_1, false, true, w, K, M, x, N, y, ldy, algo, s);
+    return mul_mat_blk32_dev(ROW_Q4_1, Blk32::Q4_1, w, K, M, x, N, y, ldy, algo, s);
 }
 static int mul_mat_q5_0_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
                             hipStream_t s) {
-    return mul_mat_q5x_dev(ROW_Q5_0, true, false, w, K, M, x, N, y, ldy, algo, s);
+    return mul_mat_blk32_dev(ROW_Q5_0, Blk32::Q5_0, w, K, M, x, N, y, ldy, algo, s);
 }
 static int mul_mat_q5_1_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
                             hipStream_t s) {
-    return mul_mat_q5x_dev(ROW_Q5_1, true, true, w, K, M, x, N, y, ldy, algo, s);
+    return mul_mat_blk32_dev(ROW_Q5_1, Blk32::Q5_1, w, K, M, x, N, y, ldy, algo, s);
 }
 
 // Q5_K (qh) / Q4_K (q45_k.hip, q45_k_gemm.hip): algo 6 = the q8_K values of x and their sub-block sums' digits as

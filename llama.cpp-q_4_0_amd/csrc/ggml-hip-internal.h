@@ -137,6 +137,12 @@ int current_device();
 hipStream_t resolve_stream(void *stream);
 void *pool_malloc(int id, size_t size, size_t *actual);
 void pool_free(int id, void *p, size_t size);
+// the qs / d / s planes of a quantized x in a workspace for (K, N) (ggml-hip-core.cpp)
+struct XPlanes {
+    int8_t *qs;
+    float *d, *s;
+};
+XPlanes x_planes(void *ws, int64_t K, int64_t N);
 size_t ws_d16_offset(int64_t K, int64_t N);
 size_t workspace_bytes(int64_t K, int64_t N);
 size_t workspace_bytes_q81(int64_t K, int64_t N);     // the exact and GEMM arms of Q4_1 / Q5_1: q8_1 planes, 40 B per block

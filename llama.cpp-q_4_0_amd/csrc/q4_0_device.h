@@ -167,6 +167,12 @@ __device__ __forceinline__ uint32_t q8_block_lane(float4 v, uint32_t &d16, int &
            ((uint32_t)(q3 & 0xFF) << 24);
 }
 
+// four q4_0 nibbles (one per byte of q >> shift) as int8: n - 8
+__device__ __forceinline__ uint32_t nib_to_i8x4(uint32_t q, int shift) {
+    const uint32_t n = (q >> shift) & 0x0F0F0F0Fu;                 // 0..15 per byte
+    return ((n | 0x80808080u) - 0x08080808u) ^ 0x80808080u;      // n - 8 as int8, no cross-byte borrow
+}
+
 // e2m3 code of n/2 for an integer n in [-15, 15]
 // (branch-free: with e = (a >= 4) + (a >= 8), c = (a << (2 - e)) + 8e is 4a / 8 + 2a / 16 + a)
 __device__ __forceinline__ uint32_t e2m3_half(int n) {

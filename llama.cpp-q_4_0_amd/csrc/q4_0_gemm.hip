@@ -22,11 +22,6 @@ namespace ghip {
 
 static constexpr int GM_BM = 64, GM_BN = 128, GM_KB = 4, GM_WAVES = 8, GM_THREADS = GM_WAVES * 64;
 
-__device__ __forceinline__ uint32_t nib_to_i8x4(uint32_t q, int shift) {
-    const uint32_t n = (q >> shift) & 0x0F0F0F0Fu;                 // 0..15 per byte
-    return ((n | 0x80808080u) - 0x08080808u) ^ 0x80808080u;      // n - 8 as int8, no cross-byte borrow
-}
-
 __device__ __forceinline__ int gm_half_off(int r, int half) {    // byte offset of a 16-B half in a 32-B row
     return r * 32 + 16 * (half ^ ((r >> 3) & 1));
 }
@@ -280,7 +275,7 @@ __global__ __launch_bounds__(GM_THREADS, 2) void k_gemm7_q4_0(const uint8_t *__r
 // tiles once at the end in a fixed order (deterministic, x -> 2x bitwise).
 //
 // Operands, all by LDS-DMA (`buffer_load ... lds`, no register staging, no ds_write):
-//   weights: an int8 image of the q4_0 rows built per call by k_prep8_w (w = nibble - 8, exactly the
+//   weights: an int8 image of the q4_0 rows built per call by k_prep8_w (blk32_w.hip; w = nibble - 8, exactly the
 //            values the q4_0 block encodes; fp16 d copied verbatim): [M/64][nb][64 rows][32 B] with
 //            the 16-byte halves of row r swapped when (r>>3)&1, so a 1 KiB DMA lands 32 rows of one
 //            block in the conflict-free operand layout, + fp16 d_w [M/64][nb][64];
@@ -325,46 +320,6 @@ __global__ __launch_bounds__(256) void k_prep8_x(const float *__restrict__ x, in
     const int phys = (sub >> 2) ^ (int)((n >> 3) & 1);            // 16-byte half, swapped per 8 tokens
     reinterpret_cast<uint32_t *>(ximg)[((b * Np + n) * 32 + 16 * phys + 4 * (sub & 3)) >> 2] = packed;
     if (sub == 0) xd16[b * Np + n] = (uint16_t)d16;
-}
-
-// weights: one lane per (row, block pair); a wave = 64 consecutive rows of one pair (coalesced 2 KiB
-// image stores per block).  Rows >= M of the last tile are written as zeros (d = 0).
-__global__ __launch_bounds__(256) void k_prep8_w(const uint8_t *__restrict__ W, int64_t rowbytes, int nb, int M,
-                                                  int8_t *__restrict__ wimg, uint16_t *__restrict__ wd16) {
-    const int r = threadIdx.x & 63;
-    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);     // (row tile, pair)
-    const int npair = nb >> 1;
-    const int64_t rt = item / npair;
-    const int p = (int)(item - rt * npair);
-    const int64_t row = rt * 64 + r;
-    if (rt * 64 >= M) return;
-    u32x4 a = {0u, 0u, 0u, 0u}, b = {0u, 0u, 0u, 0u};
-    uint32_t c = 0u;
-    if (row < M) {
-        const uint8_t *src = W + row * rowbytes + (int64_t)p * 36;
-        a = *reinterpret_cast<const u32x4 *>(src);      // dword-aligned 36-byte pair (rows are 36*nb/2 B)
-        b = *reinterpret_cast<const u32x4 *>(src + 16);
-        c = *reinterpret_cast<const uint32_t *>(src + 32);
-    }
-    // block 2p: d = a.x[15:0], qs = bytes 2..17; block 2p+1: d = b.x[31:16], qs = b.y..c
-    const uint32_t e[4] = {__builtin_amdgcn_alignbyte(a.y, a.x, 2), __builtin_amdgcn_alignbyte(a.z, a.y, 2),
-                           __builtin_amdgcn_alignbyte(a.w, a.z, 2), __builtin_amdgcn_alignbyte(b.x, a.w, 2)};
-    const uint32_t o[4] = {b.y, b.z, b.w, c};
-    const int sw = (r >> 3) & 1;
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const uint32_t *q = k ? o : e;
-        u32x4 lo, hi;                                    // elements 0..15 (low nibbles), 16..31 (high)
-        lo.x = nib_to_i8x4(q[0], 0); lo.y = nib_to_i8x4(q[1], 0); lo.z = nib_to_i8x4(q[2], 0); lo.w = nib_to_i8x4(q[3], 0);
-        hi.x = nib_to_i8x4(q[0], 4); hi.y = nib_to_i8x4(q[1], 4); hi.z = nib_to_i8x4(q[2], 4); hi.w = nib_to_i8x4(q[3], 4);
-        if (row >= M) lo = hi = u32x4{0u, 0u, 0u, 0u};
-        const int64_t blk = rt * nb + 2 * p + k;
-        u32x4 *dst = reinterpret_cast<u32x4 *>(wimg + (blk * 64 + r) * 32);
-        dst[sw] = lo;
-        dst[sw ^ 1] = hi;
-        const uint32_t d = k ? (b.x >> 16) : (a.x & 0xFFFFu);
-        wd16[blk * 64 + r] = (uint16_t)(row < M ? d : 0u);
-    }
 }
 
 // Schedule (round 3, tools/r3_g8var.sh, kernel medians at 4096x4096x512: 33.3 -> 29.2 us): the i8
@@ -553,18 +508,6 @@ hipError_t gemm8_prep_x(const float *x, int64_t K, int64_t N, void *xws, hipStre
     uint16_t *xd16 = (uint16_t *)((char *)xws + (size_t)nb * Np * 32);
     (void)hipGetLastError();
     launch_k(k_prep8_x, dim3((unsigned)((nb + 3) / 4), (unsigned)((N + 7) / 8)), dim3(256), 0, s, x, K, N, ximg, xd16, Np);
-    return hipGetLastError();
-}
-
-hipError_t gemm8_prep_w(const void *W, int64_t K, int64_t M, void *wws, hipStream_t s) {
-    const int nb = (int)(K / QK);
-    const int64_t Mt = (M + 63) / 64;
-    int8_t *wimg = (int8_t *)wws;
-    uint16_t *wd16 = (uint16_t *)((char *)wws + (size_t)Mt * nb * 2048);
-    (void)hipGetLastError();
-    const int64_t items = Mt * (nb / 2);                  // (row tile, pair) items, 4 per 256-thread block
-    launch_k(k_prep8_w, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, (const uint8_t *)W, (int64_t)nb * Q4B, nb,
-             (int)M, wimg, wd16);
     return hipGetLastError();
 }
 

@@ -153,7 +153,7 @@ hipError_t quantize_q8_K_planes(const float *x, int64_t K, int64_t N, void *qs, 
 hipError_t gemm_q6_K(const void *W, int64_t K, int64_t M, const void *xqs, const float *xd, int64_t N, float *y,
                      int64_t ldy, hipStream_t s);
 
-// Q8_0 weights (q8_0_w.hip): the layer matrices of a "mostly Q8_0" file.  W: ggml block_q8_0 rows, verbatim
+// Q8_0 weights (blk32_w.hip): the layer matrices of a "mostly Q8_0" file.  W: ggml block_q8_0 rows, verbatim
 // (34 bytes per 32 weights, rows 4-byte aligned: K % 64 == 0).
 hipError_t dequantize_q8_0(const void *wq, int64_t K, int64_t M, float *w, hipStream_t s);
 // fused q8_0 quantize of x (LDS) + q8_0.q8_0 GEMV; N > gemv_q8_0w_max_tokens(K) runs column tiles (a column's y
@@ -189,7 +189,7 @@ hipError_t quantize_q8_K_digit_planes(const float *x, int64_t K, int64_t N, void
 hipError_t gemm_q45_K(bool qh, const void *W, int64_t K, int64_t M, const void *xqs, const float *xd, const void *xdig,
                       int64_t N, float *y, int64_t ldy, const DeviceInfo &dev, hipStream_t s);
 
-// Q4_1 / Q5_0 / Q5_1 weights (q5x_w.hip): the layer matrices of a "mostly Q4_1 / Q5_0 / Q5_1" file.  W: ggml
+// Q4_1 / Q5_0 / Q5_1 weights (blk32_w.hip): the layer matrices of a "mostly Q4_1 / Q5_0 / Q5_1" file.  W: ggml
 // block_q4_1 (20 bytes per 32 weights), block_q5_0 (22) or block_q5_1 (24) rows, verbatim, 4-byte aligned (K % 64
 // == 0); qh: the type has a fifth bit plane (Q5_0, Q5_1), mn: a minimum and q8_1 activations (Q4_1, Q5_1).
 // dequantize_row_q4_1 / _q5_0 / _q5_1, bit-exact

@@ -1,6 +1,6 @@
 // q5x_gemm.hip — the prefill GEMM of the Q4_1 / Q5_1 x F32 mul_mat (gfx950, wave64): k_gemm_q5x1 on the int8
 // matrix cores, one template parameter QH (true: Q5_1, false: Q4_1).  Q5_0 has no part in it: its activations are
-// q8_0 and it takes k_gemm8 (q5x_w.hip).
+// q8_0 and it takes k_gemm8 (blk32_w.hip).
 //
 // Per output y[n][m], from acc = +0, the blocks b = 0 .. K / 32 - 1 of 32 elements in order:
 //   acc = fmaf((float)isum_b, d_w[m][b] * d_x[n][b], acc)        (the product one rounded f32 multiply)
@@ -8,14 +8,14 @@
 // isum_b = sum q q8 over the block, q the UNSIGNED 0..15 / 0..31 used as int8 and q8 the q8_1 byte: one
 // v_mfma_i32_32x32x32_i8 spans exactly one block, so isum_b comes off the matrix core as an exact int32 (at most
 // 32 * 31 * 127 < 2^17, exact in fp32); d_x = amax / 127 unrounded and s_x = d_x * (float)sum q8 are
-// quantize_q8_1_soa's planes (the bits of quantize_row_q8_1).  This is the per-block step of the GEMV (k_gemv_q5x):
+// quantize_q8_1_soa's planes (the bits of quantize_row_q8_1).  This is the per-block step of the GEMV (k_gemv_blk32):
 // a block's two large, opposite terms stay adjacent.  It runs as ONE chain per output, where the GEMV runs 64 lane
 // chains and a tree, so y is not bitwise the GEMV's (it is within the parity bound of it, as Q8_0's and Q5_0's
 // GEMMs are of their GEMVs).  K is never split across waves or workgroups, so y depends on nothing but (row,
 // column, K): not on the tile shape, the grid, M, N or a column's position in the call.
 //
 // Weights are read in place (no image, no workspace of their own).  K % 64 == 0 and nothing more: a row is a whole
-// number of block PAIRS of 40 / 48 bytes, 4-byte aligned and nothing more (load_pairx, q5x_device.h).  A stage is
+// number of block PAIRS of 40 / 48 bytes, 4-byte aligned and nothing more (load_pairx, blk32_device.h).  A stage is
 // G5G_SP = 4 pairs = 256 elements: the first 256 threads of the workgroup each load one (row, pair) of the 64-row
 // tile (the four pairs of a row on neighbouring lanes: 160 / 192 contiguous bytes), decode it (q5x_decode_pair) and
 // store the 64 bytes in element order into the LDS plane, with d_w and m_w of the two blocks as f32 beside it; every
@@ -31,7 +31,7 @@
 // d_x / s_x [8][BN] f32, block-major, so a lane's d_w is conflict-free and the four columns of a D register group
 // are one ds_read_b128 (two addresses per wave: a broadcast).  One stage in a single LDS buffer; the next stage's
 // global loads are issued before the current one's MFMAs.
-#include "q5x_device.h"
+#include "blk32_device.h"
 
 namespace ghip {
 

@@ -6,11 +6,11 @@ _q5_1), independent of the device.  Per output y[n][m], from acc = +0, the block
 
 isum_b is the exact integer sum of the block's 32 products of the stored weight value (0..15 / 0..31) and the q8_1
 byte, at most 32 * 31 * 127 < 2^17.  Both fma products are exact in float64 (17 x 24 and 11 x 24 bits), so
-q8_0w_ref.fmaf32 is a correctly rounded fma for them."""
+blk32_ref.fmaf32 is a correctly rounded fma for them."""
 import numpy as np
 
 import q5x_ref as R
-from q8_0w_ref import fmaf32
+from blk32_ref import fmaf32
 
 
 def chain(t, wq, xq, K):

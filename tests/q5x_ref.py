@@ -9,8 +9,8 @@ A type is named by its fixture variant: "q41", "q50", "q51".  Q5_0 multiplies ag
 (oracle.quantize_q8_0), the two types with a minimum against q8_1: f32 d, f32 s, qs[32] (40 bytes)."""
 import numpy as np
 
+from blk32_ref import fmaf32, gemv_lane_chains
 from parity import split_q8_0
-from q8_0w_ref import fmaf32
 
 QK = 32
 Q81B = 40
@@ -187,6 +187,18 @@ def vec_dot_avx2(t, wq, xq, K, summs_fma=False):
         r = (r[:, :, 0:2] + r[:, :, 2:4]).astype(np.float32)
         r = (r[:, :, 0] + r[:, :, 1]).astype(np.float32)
         return (r + summs).astype(np.float32) if has_min(t) else r
+
+
+def gemv_schedule(t, wq, x, K):
+    """f32 [N, M]: k_gemv_blk32's own fp32 order on weights of type t against f32 x [N, K].  x per block: Q5_0 takes
+    q8_block_lane's bytes with d_x = fp32(fp16(amax / 127.f)), and its block sum has the integer 16 * sum q taken off
+    (here: the weights as q - 16, the same integer); the types with a minimum take the unrounded d_x = amax / 127.f
+    and s_x = d_x * (float)sum q, one rounded multiply (quantize_q8_1).  The lane chains and the tree are
+    blk32_ref.gemv_lane_chains."""
+    dw, mw, dx, sx, lanes = _lane_sums(t, wq, quantize_x(t, x), K)
+    isum = lanes.sum(axis=3).astype(np.float32)         # exact: |isum| <= 32 * 31 * 127 < 2^24
+    dd = (dw[None, :, :] * dx[:, None, :]).astype(np.float32)
+    return gemv_lane_chains(isum, dd, mw, sx) if has_min(t) else gemv_lane_chains(isum, dd)
 
 
 def _pack(t, d, m, q):

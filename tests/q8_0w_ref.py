@@ -5,6 +5,7 @@ bit; tests/test_q8_0w_ref.py checks both against the fixtures the compiled refer
 restates (oracle.quantize_q8_0, bit-exact)."""
 import numpy as np
 
+from blk32_ref import fmaf32, gemv_lane_chains
 from parity import split_q8_0
 
 QK = 32
@@ -60,22 +61,6 @@ def block_terms(wq, xq, K):
     return t.sum(axis=2), np.abs(t).sum(axis=2)
 
 
-def fmaf32(a, b, c):
-    """float32 fma(a, b, c), correctly rounded, for float32 arrays whose product a * b is exact in float64 (here: a
-    24-bit scale times an integer below 2^17).  p + c is formed in float64 rounded to ODD (TwoSum gives the
-    rounding error; an inexact even result moves to its odd neighbour), so that the final rounding to float32
-    is the single rounding of the exact sum (53 >= 2 * 24 + 2 bits)."""
-    p = a.astype(np.float64) * b.astype(np.float64)
-    c = c.astype(np.float64)
-    s = p + c
-    bb = s - p
-    err = (p - (s - bb)) + (c - bb)
-    other = np.nextafter(s, np.where(err > 0, np.inf, -np.inf))
-    even = (s.view(np.int64) & 1) == 0
-    s = np.where((err != 0) & even, other, s)
-    return s.astype(np.float32)
-
-
 def vec_dot_avx2(wq, xq, K):
     """f32 [N, M]: the AVX2 branch of ggml_vec_dot_q8_0_q8_0, bit for bit: per block, d = fp32(d_w) * fp32(d_x)
     rounded to float32, acc_j = fmaf(d, (float)lane_j, acc_j) for the eight lanes, blocks in order, then
@@ -91,6 +76,16 @@ def vec_dot_avx2(wq, xq, K):
         r = (acc[:, :, 0:4] + acc[:, :, 4:8]).astype(np.float32)
         r = (r[:, :, 0:2] + r[:, :, 2:4]).astype(np.float32)
         return (r[:, :, 0] + r[:, :, 1]).astype(np.float32)
+
+
+def gemv_schedule(wq, x, K):
+    """f32 [N, M]: k_gemv_blk32's own fp32 order on Q8_0 weights against f32 x [N, K].  x per block is q8_block_lane's:
+    the q8_0 bytes and d_x = fp32(fp16(amax / 127.f)); the lane chains and the tree are blk32_ref.gemv_lane_chains."""
+    import oracle as O
+    dw, dx, lanes = _lane_sums(wq, O.quantize_q8_0(np.ascontiguousarray(x, np.float32), "avx2"), K)
+    isum = lanes.sum(axis=3).astype(np.float32)         # exact: |isum| <= 32 * 128 * 127 < 2^24
+    dd = (dw[None, :, :] * dx[:, None, :]).astype(np.float32)
+    return gemv_lane_chains(isum, dd)
 
 
 def q4_0_as_q8_0(w4q, K):

@@ -1,4 +1,4 @@
-"""Q4_1 / Q5_0 / Q5_1 WEIGHTS x F32 mul_mat on the device (csrc/q5x_w.hip): exact mode bit-identical to the reference's
+"""Q4_1 / Q5_0 / Q5_1 WEIGHTS x F32 mul_mat on the device (csrc/blk32_w.hip): exact mode bit-identical to the reference's
 AVX2 ggml_vec_dot_q4_1_q8_1 / _q5_0_q8_0 / _q5_1_q8_1, the fused GEMV within the parity bound under every launch
 policy and tiling, Q5_0's per-call int8 image + k_gemm8 prefill path (bitwise Q8_0's on equal values), the
 dequantizers and the q8_1 quantizer, graph capture, status codes and the ggml hook path on hand-built tensors.
@@ -129,6 +129,34 @@ def test_exact_full_range_blocks_bitwise(exact_off, t):
 
 
 # ---- GEMV -------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def gemv_pin_case(t, K, M):
+    """Weights (quantized rows, the first min(M // 2, 64) of them full-range blocks with the crafted ones), 9
+    activation rows and the restated GEMV order on them: computed once per type and shape, shared by the token
+    counts."""
+    rng = rng_for(20, GTYPE[t], K, M)
+    wq = quantized_weights(t, rng, M, K)
+    ns = min(M // 2, 64)
+    if ns:
+        wq[:ns] = R.random_blocks(rng, ns, K, R.has_qh(t), R.has_min(t), special=True)
+    x = rng.standard_normal((9, K)).astype(np.float32)
+    y = R.gemv_schedule(t, wq, x, K)
+    for a in (wq, x, y):
+        a.setflags(write=False)
+    return wq, x, y
+
+
+@pytest.mark.parametrize("N", [1, 3, 8, 9])
+@pytest.mark.parametrize("K,M", [(64, 1), (64, 8209), (4160, 33)])
+@pytest.mark.parametrize("t", TYPES)
+def test_gemv_bitwise_restated_schedule(exact_off, t, K, M, N):
+    """algo = GEMV is bitwise q5x_ref.gemv_schedule.  K = 64: one pair and 63 idle lanes; 4160: 65 pairs, a second
+    chunk of one pair; M = 8209 at K = 64: more rows than waves under the auto grid rule, so the ring crosses
+    row ends; M = 33: the last workgroup holds one row; N = 8: the full token tile, 9: a tile of 8 and one of 1."""
+    wq, x, y_ref = gemv_pin_case(t, K, M)
+    assert_bitwise(gpu_mul_mat(t, wq, K, x[:N], algo=GEMV), y_ref[:N])
+
 
 @functools.lru_cache(maxsize=None)
 def gemv_case(t, K):

@@ -1,4 +1,4 @@
-"""Q8_0 WEIGHTS x F32 mul_mat on the device (csrc/q8_0_w.hip): exact mode bit-identical to the reference's AVX2
+"""Q8_0 WEIGHTS x F32 mul_mat on the device (csrc/blk32_w.hip): exact mode bit-identical to the reference's AVX2
 ggml_vec_dot_q8_0_q8_0, the fused GEMV within the parity bound under every launch policy and tiling, the
 per-call int8 image + k_gemm8 prefill path (bitwise the q4_0 path's on equal values), the dequantizer, graph
 capture, status codes and the ggml hook path on hand-built tensors.  References: the fixtures the compiled
@@ -119,6 +119,32 @@ def test_exact_full_range_weights_bitwise(exact_off):
 
 
 # ---- GEMV -------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def gemv_pin_case(K, M):
+    """Weights (quantized rows, the first min(M // 2, 64) of them full-range blocks with the crafted ones), 9
+    activation rows and the restated GEMV order on them: computed once per shape, shared by the token counts."""
+    rng = rng_for(20, K, M)
+    wq = quantized_weights(rng, M, K)
+    ns = min(M // 2, 64)
+    if ns:
+        wq[:ns] = R.random_q8_0(rng, ns, K, special=True)
+    x = rng.standard_normal((9, K)).astype(np.float32)
+    y = R.gemv_schedule(wq, x, K)
+    for a in (wq, x, y):
+        a.setflags(write=False)
+    return wq, x, y
+
+
+@pytest.mark.parametrize("N", [1, 3, 8, 9])
+@pytest.mark.parametrize("K,M", [(64, 1), (64, 8209), (4160, 33)])
+def test_gemv_bitwise_restated_schedule(exact_off, K, M, N):
+    """algo = GEMV is bitwise q8_0w_ref.gemv_schedule.  K = 64: one pair and 63 idle lanes; 4160: 65 pairs, a second
+    chunk of one pair; M = 8209 at K = 64: more rows than waves under the auto grid rule, so the ring crosses
+    row ends; M = 33: the last workgroup holds one row; N = 8: the full token tile, 9: a tile of 8 and one of 1."""
+    wq, x, y_ref = gemv_pin_case(K, M)
+    assert_bitwise(gpu_mul_mat(wq, K, x[:N], algo=GEMV), y_ref[:N])
+
 
 @functools.lru_cache(maxsize=None)
 def gemv_case(K):

@@ -96,6 +96,25 @@ def test_ref_crafted_blocks(t):
     assert (y[3] == 0).all() and (y[:, 3] == 0).all()
 
 
+@pytest.mark.parametrize("t", TYPES)
+def test_gemv_schedule_properties(t):
+    """The restated GEMV order (64 lane chains and the wave tree): within the parity bound of the exact-mode
+    restatement on the same inputs, x -> 2x bitwise, and a row's and a column's y independent of what is passed with
+    it.  K = 64: one pair; 4160: 65 pairs (lane 0 a two-pair chain); 11008: 172 pairs."""
+    from parity import check_y
+    for K in (64, 4160, 11008):
+        rng = np.random.default_rng([0x51, 2, R.TYPES[t][0], K])
+        M, N = 7, 3
+        wq = R.random_blocks(rng, M, K, R.has_qh(t), R.has_min(t))
+        x = rng.standard_normal((N, K)).astype(np.float32)
+        y = R.gemv_schedule(t, wq, x, K)
+        xq = R.quantize_x(t, x)
+        check_y(y, R.vec_dot_avx2(t, wq, xq, K), R.block_terms(t, wq, xq, K)[1], rtol=1e-3, atol_blocks=1e-6)
+        assert np.array_equal(bits(R.gemv_schedule(t, wq, 2 * x, K)), bits(2 * y))
+        assert np.array_equal(bits(R.gemv_schedule(t, wq[2:5], x[1:2], K)), bits(y[1:2, 2:5]))
+        assert np.any(y != 0)
+
+
 def test_random_blocks_hold_the_specials():
     for t in TYPES:
         wq = R.random_blocks(np.random.default_rng([0x51, 1]), 5, 256, R.has_qh(t), R.has_min(t))

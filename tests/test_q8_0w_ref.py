@@ -87,6 +87,25 @@ def test_fmaf32_matches_libm():
            bits(np.float32([libm.fmaf(1.5, 1.0, math.ldexp(1.0, 24))]))[0]
 
 
+def test_gemv_schedule_properties():
+    """The restated GEMV order (64 lane chains and the wave tree): within the parity bound of the exact-mode
+    restatement on the same inputs, x -> 2x bitwise, and a row's and a column's y independent of what is passed with
+    it.  K = 64: one pair; 4160: 65 pairs (lane 0 a two-pair chain); 11008: 172 pairs."""
+    import oracle as O
+    from parity import check_y
+    for K in (64, 4160, 11008):
+        rng = np.random.default_rng([0x80, 3, K])
+        M, N = 7, 3
+        wq = R.random_q8_0(rng, M, K)
+        x = rng.standard_normal((N, K)).astype(np.float32)
+        y = R.gemv_schedule(wq, x, K)
+        xq = O.quantize_q8_0(x, "avx2")
+        check_y(y, R.vec_dot_avx2(wq, xq, K), R.block_terms(wq, xq, K)[1], rtol=1e-3, atol_blocks=1e-6)
+        assert np.array_equal(bits(R.gemv_schedule(wq, 2 * x, K)), bits(2 * y))
+        assert np.array_equal(bits(R.gemv_schedule(wq[2:5], x[1:2], K)), bits(y[1:2, 2:5]))
+        assert np.any(y != 0)
+
+
 def test_q4_0_as_q8_0_keeps_the_values():
     import oracle as O
     from parity import split_q4_0

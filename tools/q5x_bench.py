@@ -12,7 +12,7 @@ over rounds), TB/s of weight bytes, and the fraction of 8 TB/s (the bound: these
 operations); per arm the time of one layer's seven launches.
 
 Prefill (profiles/q5x_gemm.json).  Q5_0 on the same three shapes, N = 9 .. 128: algo 1 (GEMV tiles of 8 columns, 4 at
-K = 11008) against algo 2 (gemm8_prep_x + k_prep8_w_q5_0 + k_gemm8: the weight-image launch is inside the timed
+K = 11008) against algo 2 (gemm8_prep_x + k_prep8_w<W5x<true, false>> + k_gemm8: the weight-image launch is inside the timed
 arm), graphs of --launches calls, warm, interleaved as above.  Per shape `min_n` is the smallest swept N from which
 the GEMM arm wins at every larger swept N; the file's `min_n` is the largest of them (the value for the default of
 GGML_HIP_Q5_0_GEMM_MIN_N), null if the GEMM does not win on every shape at the largest N.  The two arms are checked
@@ -172,7 +172,7 @@ def prefill(L, s, a):
     per_shape = [sh["min_n"] for sh in shapes]
     return {"bench": "q5x_gemm", "type": "q5_0", "launches_per_graph": a.launches, "rounds": a.rounds,
             "settle_ms": a.settle_ms, "shapes": shapes, "min_n": None if None in per_shape else max(per_shape),
-            "gemm_arm": "gemm8_prep_x + k_prep8_w_q5_0 (weight image per call) + k_gemm8",
+            "gemm_arm": "gemm8_prep_x + k_prep8_w<W5x<true, false>> (weight image per call) + k_gemm8",
             "timing": "warm HIP-graph replays, device events, arms interleaved, median over rounds"}
 
 
@@ -231,7 +231,7 @@ def prefill1(L, s, a):
             "min_n_note": "the smallest swept N from which algo 7 wins on every shape of both types at every larger "
                           "swept N: the recommended GGML_HIP_Q41_Q51_GEMM_MIN_N (the default is never)",
             "gemm_arm": "quantize_q8_1_soa + k_gemm_q5x1 (weights read in place)",
-            "q5_0_gemm8_arm": "Q5_0, same shape: gemm8_prep_x + k_prep8_w_q5_0 (weight image per call) + k_gemm8",
+            "q5_0_gemm8_arm": "Q5_0, same shape: gemm8_prep_x + k_prep8_w<W5x<true, false>> (weight image per call) + k_gemm8",
             "timing": "warm HIP-graph replays, device events, arms interleaved, median over rounds"}
 
 

@@ -11,7 +11,7 @@ device events.  Reported per shape and arm: microseconds per launch (median, min
 weight bytes, and the fraction of 8 TB/s.
 
 Prefill (profiles/q8_0_gemm.json).  M = K = 4096, N = 9 .. 512: algo 1 (GEMV tiles of 8 columns) against algo 2
-(gemm8_prep_x + k_prep8_w_q8_0 + k_gemm8: the weight-image launch is inside the timed arm), graphs of --launches
+(gemm8_prep_x + k_prep8_w<W8_0> + k_gemm8: the weight-image launch is inside the timed arm), graphs of --launches
 calls, warm, interleaved as above.  `min_n` is the smallest swept N from which the GEMM arm wins at every larger
 swept N (the value for the default of q8_0_gemm_min_n); null if it never does.  The two arms are checked against
 each other within 1e-3 of the largest |y| before they are timed.  Fails without a HIP device.
@@ -159,7 +159,7 @@ def prefill(L, s, a):
         min_n = row["N"]
     return {"bench": "q8_0_gemm", "K": K, "M": M, "weight_bytes": M * (K // 32) * 34, "launches_per_graph": a.launches,
             "rounds": a.rounds, "settle_ms": a.settle_ms, "sweep": sweep, "min_n": min_n,
-            "gemm_arm": "gemm8_prep_x + k_prep8_w_q8_0 (weight image per call) + k_gemm8",
+            "gemm_arm": "gemm8_prep_x + k_prep8_w<W8_0> (weight image per call) + k_gemm8",
             "timing": "warm HIP-graph replays, device events, arms interleaved, median over rounds"}
 
 
