@@ -326,8 +326,9 @@ bool try_fuse(tensor *t) {
         c.out = (float *)dptr(t);
         c.ncols = t->ne[0];
         auto al = [](const void *q) { return ((uintptr_t)q & 15) == 0; };
-        bool fold = norm_fold_enabled() && !exact_mode() && gabi::nrows(t) == 1 && c.ncols % 64 == 0 &&
-                    c.ncols <= 16384 && al(c.a) && al(c.b) && al(c.sum) && al(c.norm) && al(c.w) && al(c.out);
+        // (only at the widths the prologue runs: a wider chain is its own launch below, then the plain GEMV)
+        bool fold = norm_fold_enabled() && !exact_mode() && gabi::nrows(t) == 1 && ghip::gemv_norm_supported(1, c.ncols) &&
+                    al(c.a) && al(c.b) && al(c.sum) && al(c.norm) && al(c.w) && al(c.out);
         // the chain's outputs must not alias its inputs (the GEMV's workgroups read the inputs while
         // workgroup 0 stores the outputs)
         for (const tensor *o : {add, (const tensor *)last, (const tensor *)t})
@@ -471,8 +472,8 @@ bool try_fuse(tensor *t) {
         c.table = tb.silu;
         c.ncols = t->ne[0];
         auto al = [](const void *q) { return ((uintptr_t)q & 15) == 0; };
-        bool fold = silu_fold_enabled() && !exact_mode() && gabi::nrows(t) == 1 && c.ncols % 64 == 0 &&
-                    c.ncols <= 16384 && al(c.a) && al(c.b) && al(c.norm) && al(c.out);
+        bool fold = silu_fold_enabled() && !exact_mode() && gabi::nrows(t) == 1 && ghip::gemv_norm_supported(2, c.ncols) &&
+                    al(c.a) && al(c.b) && al(c.norm) && al(c.out);
         for (const tensor *o : {(const tensor *)last, (const tensor *)t})
             for (const tensor *i : {(const tensor *)last->src0, (const tensor *)t->src1})
                 if (dev_overlap(o, i)) fold = false;

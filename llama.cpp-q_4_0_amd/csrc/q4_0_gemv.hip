@@ -392,7 +392,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv_q4_0(const float *__restric
             const float scale = 1.0f / (float)__builtin_sqrt((double)(mean + 1e-6f));
             const bool store = blockIdx.x == 0;
 #pragma unroll
-            for (int i = 0; i < GEMV_XPRO; i++) {
+            for (int i = 0; i < GEMV_XPRO_N; i++) {
                 const int idx = tid + i * XT;
                 if (idx < total) {
                     const float4 xv4 = v[i];
@@ -860,12 +860,18 @@ static hipError_t launch_gemv_norm(const GemvMats &m, int64_t K, const float *b,
                    : launch_gemv_w<1, GEMV_WAVES, 1, VAR, PPL, 1>(m, K, b, dev, s, &nrm);
 }
 
+bool gemv_norm_supported(int kind, int64_t K) {
+    if ((kind != 1 && kind != 2) || K < 64 || K % 64 != 0) return false;
+    // one round of x-waves holds the row: K / 4 float4 <= 16 waves * 64 lanes * GEMV_XPRO[_N]
+    if (K / 4 > GEMV_WAVES * 64 * (kind == 1 ? GEMV_XPRO_N : GEMV_XPRO)) return false;
+    return (K / 64 + 63) / 64 <= 3;     // row items of at most 3 pairs per lane (the instantiated forms)
+}
+
 hipError_t gemv_q4_0_multi_norm(int nmat, const void *const *W, const int64_t *M, int64_t K, const float *b,
                                 const GemvNorm &nrm, float *const *y, const int64_t *ldy, const DeviceInfo &dev,
                                 hipStream_t s, const GemvEpi *epi) {
-    // one round of x-waves holds the row: K / 4 float4 <= 16 waves * 64 lanes * GEMV_XPRO
-    if (nmat < 1 || nmat > GEMV_MAXMAT || K % 64 != 0 || K / 4 > 16 * 64 * (nrm.kind == 1 ? GEMV_XPRO_N : GEMV_XPRO) || !b ||
-        (nrm.kind == 1 && !nrm.w) || (nrm.kind == 2 && (!nrm.a || !nrm.table)) || (nrm.kind != 1 && nrm.kind != 2))
+    if (nmat < 1 || nmat > GEMV_MAXMAT || !gemv_norm_supported(nrm.kind, K) || !b ||
+        (nrm.kind == 1 && !nrm.w) || (nrm.kind == 2 && (!nrm.a || !nrm.table)))
         return hipErrorInvalidValue;
     GemvMats m{};
     m.n = nmat;
@@ -898,7 +904,7 @@ hipError_t gemv_q4_0_multi_norm(int nmat, const void *const *W, const int64_t *M
         if (ppl == 2) return launch_gemv_norm<3, 2>(m, K, b, dev, s, nrm, rd, epi);
         if (ppl == 3) return launch_gemv_norm<3, 3>(m, K, b, dev, s, nrm, rd, epi);
     }
-    return hipErrorInvalidValue;        // K > 12288: chunked items are not instantiated with the prologue
+    return hipErrorInvalidValue;        // not reached (gemv_norm_supported): no chunked items with the prologue
 }
 
 }  // namespace ghip

@@ -42,7 +42,9 @@ constexpr int GEMV_MULTI_MAX = 4;
 hipError_t gemv_q4_0_multi(int nmat, const void *const *W, const int64_t *M, int64_t K, const float *x, int64_t N,
                            float *const *y, const int64_t *ldy, const DeviceInfo &dev, hipStream_t s);
 
-// The same for N = 1 with the chain that produces x folded into the x prologue (K <= 16384); the
+// The same for N = 1 with the chain that produces x folded into the x prologue, at the widths
+// gemv_norm_supported(kind, K) accepts (K % 64 == 0; kind 1: K <= 8192, one round of 16 x-waves with the
+// default GEMV_XPRO_N holds the row; kind 2: K <= 12288, the row-item forms of at most 3 pairs per lane); the
 // GEMVs consume x, and workgroup 0 also stores the chain's tensors (each may be null) bit for bit as
 // the unfused launches:
 //   kind 1, ggml's [add ->] rms_norm -> mul(norm weight row): x = (a ? a + b : b) -> sum,
@@ -73,6 +75,9 @@ struct GemvEpi {
     int kind[GEMV_MULTI_MAX], f16[GEMV_MULTI_MAX], ne0[GEMV_MULTI_MAX];
     int ne10[GEMV_MULTI_MAX], ne11[GEMV_MULTI_MAX], nb10[GEMV_MULTI_MAX], nb11[GEMV_MULTI_MAX], nb12[GEMV_MULTI_MAX];
 };
+// the kinds and widths gemv_q4_0_multi_norm launches (everything else: hipErrorInvalidValue, nothing launched);
+// the hook scheduler holds a chain for the prologue only where this is true
+bool gemv_norm_supported(int kind, int64_t K);
 // epi: nullptr, or the epilogue of every matrix (strided row mapping; returns hipErrorInvalidValue where the
 // launch shape cannot pair rows e and e ^ 1 inside one workgroup)
 hipError_t gemv_q4_0_multi_norm(int nmat, const void *const *W, const int64_t *M, int64_t K, const float *b,

@@ -9,12 +9,20 @@ through ggml_hip_debug_gemv_norm:
 * EPI 2 (w1|w3 behind the ffn norm, interleaved gate / up rows): silu -> mul in the epilogue, bitwise
   ggml_hip's own silu -> mul launch on the same gate / up (ggml's fp16 silu table), blocked (default) and
   strided (GEMV map 0) pairs.
+In both, the y of the launch without the epilogue (the rms_norm prologue alone) is bitwise the plain GEMV (kind 0) of
+the numpy restatement of the chain (tests/ggml_ops_ref.py), so the epilogue tests do not rest on the prologue alone;
+tests/test_gpu_gemv_prologue.py pins the prologue itself.  Model shapes and the smallest ones (K = 64, two rows per
+matrix, one head); a member with an odd row count is refused with nothing launched.
 The model-level tests (tests/test_gpu_llama_ggjt.py) pin the whole chain to the reference's logits."""
 import ctypes
 
 import numpy as np
 import pytest
 
+import ggml_ops_ref as R
+from gemv_norm_util import (EPI_GLU_CASES, EPI_ROPE_CASES, GemvEpi, gemv_norm, gemv_norm_rc, rand_q4, sentinel_buf,
+                            untouched)
+from ggml_ops_ref import assert_bits
 from hip_env import ggml_hip, gpu_available
 
 pytestmark = [pytest.mark.gpu,
@@ -24,37 +32,16 @@ DB = ggml_hip.DeviceBuffer
 P = ctypes.c_void_p
 
 
-class GemvEpi(ctypes.Structure):          # csrc/q4_0_kernels.h
-    _fields_ = [("glu", ctypes.c_int), ("table", P), ("d", P * 4), ("cs", P * 4), ("c", P * 4),
-                ("kind", ctypes.c_int * 4), ("f16", ctypes.c_int * 4), ("ne0", ctypes.c_int * 4),
-                ("ne10", ctypes.c_int * 4), ("ne11", ctypes.c_int * 4), ("nb10", ctypes.c_int * 4),
-                ("nb11", ctypes.c_int * 4), ("nb12", ctypes.c_int * 4)]
-
-
-def rand_q4(M, K, rng):
-    """M rows of valid q4_0 blocks: random nibbles, fp16 scales ~1e-2."""
-    nb = K // 32
-    blk = np.zeros((M, nb, 18), np.uint8)
-    d = (rng.standard_normal((M, nb)) * 0.01).astype(np.float16)
-    blk[:, :, 0:2] = d.view(np.uint8).reshape(M, nb, 2)
-    blk[:, :, 2:] = rng.integers(0, 256, (M, nb, 16), dtype=np.uint8)
-    return blk.reshape(M, nb * 18)
-
-
-def gemv_norm(L, W, Ms, K, kind, a, b, w, ys, epi=None, reps=0, extra=None):
-    L.ggml_hip_debug_gemv_norm.argtypes = [ctypes.c_int, P, P, ctypes.c_int64, ctypes.c_int, P, P, P, P, P, P, P, P,
-                                           ctypes.c_int, P]
-    n = len(W)
-    wp = (P * 4)(*[x.ptr for x in W])
-    mp = (ctypes.c_int64 * 4)(*Ms)
-    yp = (P * 4)(*[y.ptr for y in ys])
-    sc = extra or {}
-    us = ctypes.c_float(0.0)
-    ggml_hip.check(L.ggml_hip_debug_gemv_norm(n, wp, mp, K, kind, a.ptr if a else None, b.ptr, w.ptr if w else None,
-                                              sc.get("sum"), sc.get("norm"), sc.get("out"), yp,
-                                              ctypes.byref(epi) if epi is not None else None, reps,
-                                              ctypes.byref(us)), "gemv_norm")
-    return us.value
+def plain_y_of_chain(L, W, Ms, K, a, b, w):
+    """the plain GEMV (kind 0) of every matrix on the numpy chain output of the host rows [a +] b -> rms_norm -> * w;
+    the rms_norm row must be order-free (no correct double summation changes its float mean)"""
+    x = R.add(a, b) if a is not None else b
+    assert R.rms_order_free(x)
+    out = R.mul(R.rms_norm(x[None, :]), w[None, :])[0]
+    assert np.isfinite(out).all() and out.any()
+    ys = [DB(M * 4) for M in Ms]
+    gemv_norm(L, W, Ms, K, 0, None, DB.from_array(out), None, ys)
+    return [y.download((M,), np.float32) for y, M in zip(ys, Ms)]
 
 
 def rope_np(x, cs, ne0):
@@ -67,18 +54,35 @@ def rope_np(x, cs, ne0):
     return y.reshape(-1)
 
 
-@pytest.mark.parametrize("K,hd,nh,vf16", [(4096, 128, 32, True), (4096, 64, 64, False), (5120, 128, 40, True)])
+def rope_cache_epi(ys, dk, csd, kc, vc, M, hd, n_ctx, pos, vf16):
+    """rope Q in place; rope K -> dk and its F16 copy into row pos of the K cache [n_ctx][M]; V -> column pos of the
+    transposed V cache [M][n_ctx]"""
+    es = 2 if vf16 else 4
+    ep = GemvEpi()
+    ep.kind[0], ep.d[0], ep.cs[0], ep.ne0[0] = 1, ys[0].ptr, csd.ptr, hd            # rope Q in place
+    ep.kind[1], ep.d[1], ep.cs[1], ep.ne0[1] = 1, dk.ptr, csd.ptr, hd               # rope K -> dk, copy to cache
+    ep.c[1], ep.f16[1] = kc.ptr + pos * M * 2, 1
+    ep.ne10[1], ep.ne11[1], ep.nb10[1], ep.nb11[1], ep.nb12[1] = M, 1, 2, M * 2, M * 2
+    ep.kind[2] = 2                                                                   # V -> transposed cache
+    ep.c[2], ep.f16[2] = vc.ptr + pos * es, int(vf16)
+    ep.ne10[2], ep.ne11[2], ep.nb10[2], ep.nb11[2], ep.nb12[2] = 1, M, es, n_ctx * es, M * n_ctx * es
+    return ep
+
+
+@pytest.mark.parametrize("K,hd,nh,vf16", EPI_ROPE_CASES)
 def test_rope_cache_epilogue_bitwise(K, hd, nh, vf16):
     L = ggml_hip.load()
     rng = np.random.default_rng(K + hd + nh)
     M = hd * nh
     W = [DB.from_array(rand_q4(M, K, rng)) for _ in range(3)]
-    b = DB.from_array(rng.standard_normal(K).astype(np.float32))
-    a = DB.from_array(rng.standard_normal(K).astype(np.float32))
-    w = DB.from_array((1.0 + 0.1 * rng.standard_normal(K)).astype(np.float32))
+    bh, ah = rng.standard_normal(K).astype(np.float32), rng.standard_normal(K).astype(np.float32)
+    wh = (1.0 + 0.1 * rng.standard_normal(K)).astype(np.float32)
+    b, a, w = DB.from_array(bh), DB.from_array(ah), DB.from_array(wh)
     ref = [DB(M * 4) for _ in range(3)]
     gemv_norm(L, W, [M] * 3, K, 1, a, b, w, ref)
     yq, yk, yv = [r.download((M,), np.float32) for r in ref]
+    for y, p in zip((yq, yk, yv), plain_y_of_chain(L, W, [M] * 3, K, ah, bh, wh)):
+        assert_bits(y, p)                                            # the prologue's y is the plain GEMV's
     ang = rng.uniform(-3, 3, hd // 2).astype(np.float32)
     cs = np.stack([np.cos(ang), np.sin(ang)], 1).astype(np.float32)
     csd = DB.from_array(cs)
@@ -89,14 +93,7 @@ def test_rope_cache_epilogue_bitwise(K, hd, nh, vf16):
     es = 2 if vf16 else 4
     ys = [DB(M * 4) for _ in range(3)]
     dk = DB(M * 4)
-    ep = GemvEpi()
-    ep.kind[0], ep.d[0], ep.cs[0], ep.ne0[0] = 1, ys[0].ptr, csd.ptr, hd            # rope Q in place
-    ep.kind[1], ep.d[1], ep.cs[1], ep.ne0[1] = 1, dk.ptr, csd.ptr, hd               # rope K -> dk, copy to cache
-    ep.c[1], ep.f16[1] = kc.ptr + pos * M * 2, 1
-    ep.ne10[1], ep.ne11[1], ep.nb10[1], ep.nb11[1], ep.nb12[1] = M, 1, 2, M * 2, M * 2
-    ep.kind[2] = 2                                                                   # V -> transposed cache
-    ep.c[2], ep.f16[2] = vc.ptr + pos * es, int(vf16)
-    ep.ne10[2], ep.ne11[2], ep.nb10[2], ep.nb11[2], ep.nb12[2] = 1, M, es, n_ctx * es, M * n_ctx * es
+    ep = rope_cache_epi(ys, dk, csd, kc, vc, M, hd, n_ctx, pos, vf16)
     gemv_norm(L, W, [M] * 3, K, 1, a, b, w, ys, epi=ep)
     gq, gk, gv = [y.download((M,), np.float32) for y in ys]
     rq, rk = rope_np(yq, cs, hd), rope_np(yk, cs, hd)
@@ -114,16 +111,19 @@ def test_rope_cache_epilogue_bitwise(K, hd, nh, vf16):
 
 
 @pytest.mark.parametrize("map_", [-1, 0], ids=["blocked", "strided"])
-@pytest.mark.parametrize("K,M", [(4096, 11008), (5120, 13824), (4096, 1000)])
+@pytest.mark.parametrize("K,M", EPI_GLU_CASES)
 def test_glu_epilogue_bitwise(K, M, map_):
     L = ggml_hip.load()
     rng = np.random.default_rng(K + M)
     W = [DB.from_array(rand_q4(M, K, rng)) for _ in range(2)]
-    b = DB.from_array(rng.standard_normal(K).astype(np.float32))
-    w = DB.from_array((1.0 + 0.1 * rng.standard_normal(K)).astype(np.float32))
+    bh = rng.standard_normal(K).astype(np.float32)
+    wh = (1.0 + 0.1 * rng.standard_normal(K)).astype(np.float32)
+    b, w = DB.from_array(bh), DB.from_array(wh)
     ref = [DB(M * 4) for _ in range(2)]
     gemv_norm(L, W, [M] * 2, K, 1, None, b, w, ref)
     yg, yu = [r.download((M,), np.float32) for r in ref]
+    for y, p in zip((yg, yu), plain_y_of_chain(L, W, [M] * 2, K, None, bh, wh)):
+        assert_bits(y, p)                                            # the prologue's y is the plain GEMV's
     ys = [DB(M * 4) for _ in range(2)]
     su, pr = DB(M * 4), DB(M * 4)
     ep = GemvEpi()
@@ -152,3 +152,35 @@ def test_glu_epilogue_bitwise(K, M, map_):
                                                 img.ptr, img_ref.ptr), "silu_mul")
     assert np.array_equal(u32(su.download((M,), np.float32)), u32(sil.download((n_pad,), np.float32)[:M]))
     assert np.array_equal(u32(pr.download((M,), np.float32)), u32(prod_ref.download((n_pad,), np.float32)[:M]))
+
+
+@pytest.mark.parametrize("Ms", [[63, 64, 64], [64, 63, 64], [64, 64, 63], [33, 33], [34, 33]],
+                         ids=lambda m: "M" + "_".join(map(str, m)))
+def test_epilogue_refuses_an_odd_member(Ms):
+    """rows e and e ^ 1 of a member are finished together, so an odd row count in any member is refused: a non-zero
+    return and every byte of y, of the chain's tensors and of the epilogue's targets as it was"""
+    L = ggml_hip.load()
+    K, hd, n_ctx, pos = 64, 2, 8, 3
+    rng = np.random.default_rng(sum(Ms))
+    glu = len(Ms) == 2
+    Mx = max(Ms)
+    W = [DB.from_array(rand_q4(M, K, rng)) for M in Ms]
+    b = DB.from_array(rng.standard_normal(K).astype(np.float32))
+    a = None if glu else DB.from_array(rng.standard_normal(K).astype(np.float32))
+    w = DB.from_array((1.0 + 0.1 * rng.standard_normal(K)).astype(np.float32))
+    ys = [sentinel_buf(M) for M in Ms]
+    ex = {k: sentinel_buf(K) for k in ("sum", "norm", "out")}
+    sizes = (("d0", Mx), ("d1", Mx), ("kc", n_ctx * Mx), ("vc", n_ctx * Mx))
+    tg = {k: sentinel_buf(n) for k, n in sizes}
+    if glu:
+        ep = GemvEpi()
+        ep.glu = 1
+        ep.d[0], ep.d[1] = tg["d0"].ptr, tg["d1"].ptr
+    else:
+        csd = DB.from_array(np.array([[np.cos(0.5), np.sin(0.5)]], np.float32))
+        ep = rope_cache_epi(ys, tg["d1"], csd, tg["kc"], tg["vc"], Mx, hd, n_ctx, pos, False)
+    rc, _ = gemv_norm_rc(L, W, Ms, K, 1, a, b, w, ys, epi=ep, extra=ex)
+    assert rc != 0
+    assert all(untouched(y, M) for y, M in zip(ys, Ms))
+    assert all(untouched(ex[k], K) for k in ex)
+    assert all(untouched(tg[k], n) for k, n in sizes)
