@@ -12,11 +12,14 @@
  * (llama.cpp:2416-2421; ggml_vec_dot_q6_K_q8_K semantics, k_quants.c), and with
  * src0 = GGML_TYPE_Q8_0: the matrices of a "mostly Q8_0" file
  * (ggml_vec_dot_q8_0_q8_0 semantics), and with src0 = GGML_TYPE_Q5_K: the layer
- * matrices of a "mostly Q5_K" file (ggml_vec_dot_q5_K_q8_K semantics).
+ * matrices of a "mostly Q5_K" file (ggml_vec_dot_q5_K_q8_K semantics), and with
+ * src0 = GGML_TYPE_Q3_K / GGML_TYPE_Q2_K: the layer matrices of the "mostly
+ * Q3_K" and "mostly Q2_K" files (ggml_vec_dot_q3_K_q8_K / _q2_K_q8_K semantics),
+ * and with src0 = GGML_TYPE_Q4_1 / Q5_0 / Q5_1.
  * src0 = GGML_TYPE_Q4_K (a "mostly Q4_K" file) is taken on this hook path only
  * with GGML_HIP_Q4_K=1 / ggml_hip_debug_set_q4_K(1) (off by default);
  * the tensor-free ggml_hip_mul_mat_q4_K always runs.  Everything
- * else (Q2_K, Q3_K, Q4_1, Q5_0, Q5_1; Q4_K with its switch off) returns "cannot" so ggml's
+ * else (Q4_K with its switch off included) returns "cannot" so ggml's
  * CPU path runs, exactly as ggml_cuda_can_mul_mat / ggml_cuda_compute_forward
  * return false for what they do not handle.
  *
@@ -273,6 +276,27 @@ int ggml_hip_debug_set_q45k_gemm_min_n(int n);
  * value (0 / 1).  Tensors uploaded while it was on stay on the device, keep being served by
  * compute_forward after it is turned off (their data is not on the host), and are freed by ggml_hip_free_data. */
 int ggml_hip_debug_set_q4_K(int on);
+/* Q3_K / Q2_K WEIGHTS (block_q3_K rows, 110 bytes per 256 weights; block_q2_K rows, 84 bytes; dev_w 4-byte aligned,
+ * which leaves a Q3_K block at 0 or 2 mod 4: every 32-bit field is read through the aligned dwords that hold it)
+ * x F32 -> F32 with the semantics of ggml_vec_dot_q3_K_q8_K / ggml_vec_dot_q2_K_q8_K on the bit-exact q8_K of x.
+ * K % 256 == 0.  Stream-ordered and capturable (exact mode after ggml_hip_reserve_workspace).  No byte outside
+ * [dev_w, dev_w + M * (K / 256) * 110 or 84) is read.  Status codes as for the q4_0 entry points; N == 0 is a no-op.
+ * dequantize_q3_K / _q2_K: dequantize_row_q3_K (k_quants.c:531-579) / dequantize_row_q2_K (352-396), bit-exact. */
+int ggml_hip_dequantize_q3_K(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream);
+int ggml_hip_dequantize_q2_K(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream);
+/* y[n * ldy + m], ldy >= M.  algo: 0 auto (4 in exact mode and for K > 16384; else 1), 1 GEMV (K <= 16384) with the
+ * q8_K quantization of x fused in, exact int32 superblock sums and one fixed fp32 order per superblock (column
+ * tiles of 8 for N > 8, bitwise the per-tile calls; y does not depend on the launch geometry), 4 exact:
+ * bit-identical to the AVX2 branch of ggml_vec_dot_q3_K_q8_K (k_quants.c:1836-1938) / ggml_vec_dot_q2_K_q8_K
+ * (1330-1394).  There is no prefill GEMM for these types yet: prefill runs as column tiles of the GEMV.  Anything
+ * else (2, 3, 5, 6 and 7 included) -> GGML_HIP_ERR_INVALID. */
+int ggml_hip_mul_mat_q3_K(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N,
+                          float *dev_y, int64_t ldy, int algo, void *stream);
+int ggml_hip_mul_mat_q2_K(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N,
+                          float *dev_y, int64_t ldy, int algo, void *stream);
+/* debug, no device needed: the algo that algo 0 of ggml_hip_mul_mat_q3_K / _q2_K (type = GGML_TYPE_Q3_K 11 /
+ * GGML_TYPE_Q2_K 10) would run now: 1 or 4; a bad type or K -> GGML_HIP_ERR_INVALID */
+int ggml_hip_debug_q23k_auto_algo(int type, int64_t K, int64_t M, int64_t N);
 
 /* Sibling mul_mats that share the activation x (ggml graphs issue wq/wk/wv and w1/w3 on the same
  * src1): n <= 4 weight matrices of the same K, y_i = W_i x with y_i f32 [N][M_i].  One launch for

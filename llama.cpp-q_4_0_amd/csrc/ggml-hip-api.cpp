@@ -187,6 +187,37 @@ int ggml_hip_debug_set_q45k_gemm_min_n(int n) { return weight_type(gabi::TYPE_Q5
 
 int ggml_hip_debug_set_q4_K(int on) { return q4k_set_enabled(on); }
 
+// Q3_K / Q2_K (q23_k.hip)
+static int dequantize_q23k(int type, const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
+    if (const int rc = check_dequantize(type, dev_wq, K, M, dev_w); rc != GGML_HIP_OK) return rc;
+    ensure_init();
+    HIP_RET(ghip::dequantize_q23_K(type == gabi::TYPE_Q3_K, dev_wq, K, M, dev_w, resolve_stream(stream)));
+    return GGML_HIP_OK;
+}
+
+int ggml_hip_dequantize_q3_K(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
+    return dequantize_q23k(gabi::TYPE_Q3_K, dev_wq, K, M, dev_w, stream);
+}
+
+int ggml_hip_dequantize_q2_K(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream) {
+    return dequantize_q23k(gabi::TYPE_Q2_K, dev_wq, K, M, dev_w, stream);
+}
+
+int ggml_hip_mul_mat_q3_K(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N, float *dev_y,
+                          int64_t ldy, int algo, void *stream) {
+    return mul_mat_type(gabi::TYPE_Q3_K, dev_w, K, M, dev_x, N, dev_y, ldy, algo, stream);
+}
+
+int ggml_hip_mul_mat_q2_K(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N, float *dev_y,
+                          int64_t ldy, int algo, void *stream) {
+    return mul_mat_type(gabi::TYPE_Q2_K, dev_w, K, M, dev_x, N, dev_y, ldy, algo, stream);
+}
+
+int ggml_hip_debug_q23k_auto_algo(int type, int64_t K, int64_t M, int64_t N) {
+    if (type != gabi::TYPE_Q3_K && type != gabi::TYPE_Q2_K) return fail(GGML_HIP_ERR_INVALID, "type must be Q3_K or Q2_K");
+    return debug_auto_algo(type, K, M, N);
+}
+
 /* not in the public header: force the Q8_0 GEMV's launch policy (tests: every policy gives the same y bitwise) */
 int ggml_hip_debug_set_q8_0_gemv_policy(int map, int depth, int wg_per_cu) {
     ghip::gemv_q8_0w_set_policy(map, depth, wg_per_cu);

@@ -343,6 +343,10 @@ static GemmMinN g_q5_0_min_n{"GGML_HIP_Q5_0_GEMM_MIN_N", 32};
 // Q4_1 / Q5_1 (algo 7, q5x_gemm.hip): "never" by default, so auto runs the GEMV at every N until the user sets the
 // threshold (the measured crossover is in DESIGN §4b; tools/q5x_bench.py, profiles/q5x1_gemm.json)
 static GemmMinN g_q41_q51_min_n{"GGML_HIP_Q41_Q51_GEMM_MIN_N", INT_MAX};
+// Q3_K / Q2_K have no GEMM yet: their rows name the GEMV behind a threshold that is "never", so auto runs
+// the GEMV's column tiles at every N and auto_algo stays one expression (the variable is reserved for that GEMM:
+// until it exists both sides of the threshold are algo 1, so setting it changes nothing)
+static GemmMinN g_q23k_min_n{"GGML_HIP_Q23K_GEMM_MIN_N", INT_MAX};
 
 // the K a type's GEMV takes: one token's q8_K image in the LDS for the k-quants (w2 of a 30B / 65B model has K =
 // 17920 / 22016), one token's q8_0 for Q8_0
@@ -352,6 +356,7 @@ static bool gemv_takes_k_q5x(int64_t K) { return ghip::gemv_q5x_max_tokens(K) >=
 
 static MulMatSig mul_mat_q6k_dev, mul_mat_q8_0_dev, mul_mat_q5k_dev, mul_mat_q4k_dev;
 static MulMatSig mul_mat_q4_1_dev, mul_mat_q5_0_dev, mul_mat_q5_1_dev;
+static MulMatSig mul_mat_q3k_dev, mul_mat_q2k_dev;
 
 static constexpr const char *ERR_K256 = "K must be a multiple of 256 (QK_K)";
 static constexpr const char *ERR_ALIGN_Q45K = "W and x must be 16-byte, y 4-byte aligned";
@@ -384,6 +389,23 @@ static const WeightType ROW_Q4_K = {
     6, 4, &g_q45k_min_n, gemv_takes_k_kquant, mul_mat_q4k_dev,
     ERR_K256, ERR_ALIGN_Q45K, ERR_GEMV_Q45K,
     QK_K, 16, ERR_DQ_Q45K};
+
+// Q3_K / Q2_K (q23_k.hip): the matrix 4-byte aligned, which leaves a Q3_K block (110 bytes) at 0 or 2 mod 4; the
+// kernels read no byte outside the matrix.  No GEMM: algo 1 behind the "never" threshold, the exact kernel where the
+// GEMV cannot take K.
+static constexpr const char *ERR_ALIGN_Q23K = "W must be 4-byte, x 16-byte, y 4-byte aligned";
+static constexpr const char *ERR_GEMV_Q23K = "the Q3_K / Q2_K GEMV supports K <= 16384";
+static constexpr const char *ERR_DQ_Q23K = "w must be 16-byte aligned, the Q3_K / Q2_K rows 2-byte aligned";
+static const WeightType ROW_Q3_K = {
+    QK_K, 4, (int64_t)1 << 31,
+    1, 4, &g_q23k_min_n, gemv_takes_k_kquant, mul_mat_q3k_dev,
+    ERR_K256, ERR_ALIGN_Q23K, ERR_GEMV_Q23K,
+    QK_K, 2, ERR_DQ_Q23K};
+static const WeightType ROW_Q2_K = {
+    QK_K, 4, (int64_t)1 << 31,
+    1, 4, &g_q23k_min_n, gemv_takes_k_kquant, mul_mat_q2k_dev,
+    ERR_K256, ERR_ALIGN_Q23K, ERR_GEMV_Q23K,
+    QK_K, 2, ERR_DQ_Q23K};
 
 // Q4_1 / Q5_0 / Q5_1 (blk32_w.hip).  Q5_0's values q - 16 are int8 and its activations q8_0, so it takes Q8_0's GEMM
 // (algo 2).  Q4_1 and Q5_1 cannot: their activation scale is an unrounded f32 and they carry a second term m_w s_x
@@ -420,6 +442,8 @@ const WeightType *weight_type(int type) {
         case gabi::TYPE_Q8_0: return &ROW_Q8_0;
         case gabi::TYPE_Q5_K: return &ROW_Q5_K;
         case gabi::TYPE_Q4_K: return &ROW_Q4_K;
+        case gabi::TYPE_Q3_K: return &ROW_Q3_K;
+        case gabi::TYPE_Q2_K: return &ROW_Q2_K;
         default: return nullptr;
     }
 }
@@ -604,6 +628,36 @@ static int mul_mat_q5k_dev(const void *w, int64_t K, int64_t M, const float *x, 
 static int mul_mat_q4k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
                            hipStream_t s) {
     return mul_mat_q45k_dev(false, w, K, M, x, N, y, ldy, algo, s);
+}
+
+// Q3_K (q3) / Q2_K (q23_k.hip): the GEMV and the exact kernel only.  An algo the types reject is refused before
+// anything else, an empty call included.
+static int mul_mat_q23k_dev(bool q3, const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
+                            int algo, hipStream_t s) {
+    if (algo != 0 && algo != 1 && algo != 4) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1 or 4");
+    const WeightType &t = ROW_Q3_K;                      // (the two rows differ in the run function only)
+    const int rc = check_operands(t, w, K, M, x, N, y, ldy);
+    if (rc != GGML_HIP_OK || N == 0) return rc;
+    const int id = current_device();
+    if (algo == 0) algo = auto_algo(t, K, N);
+    if (algo == 1) {
+        if (!t.gemv_takes_k(K)) return fail(GGML_HIP_ERR_UNSUPPORTED, t.err_gemv_k);
+        HIP_RET(ghip::gemv_q23_K(q3, w, K, M, x, N, y, ldy, g_dev[id].info, s));
+        return GGML_HIP_OK;
+    }
+    void *ws = nullptr;
+    const int wrc = quantize_q8k_ws(id, x, K, N, s, &ws);
+    if (wrc != GGML_HIP_OK) return wrc;
+    HIP_RET(ghip::mm_exact_q23_K(q3, w, K, M, ws, N, y, ldy, s));
+    return GGML_HIP_OK;
+}
+static int mul_mat_q3k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                           hipStream_t s) {
+    return mul_mat_q23k_dev(true, w, K, M, x, N, y, ldy, algo, s);
+}
+static int mul_mat_q2k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                           hipStream_t s) {
+    return mul_mat_q23k_dev(false, w, K, M, x, N, y, ldy, algo, s);
 }
 
 // Sibling matrices (one x) that all take k_gemm9 on a registered fp6 image: ONE launch over their

@@ -157,7 +157,7 @@ void mul_mat_node(const tensor *src0, const tensor *src1, tensor *dst) {
     const WeightType *row = weight_type(wtype);          // null: Q4_0
     if (wtype == gabi::TYPE_COUNT) {
         fprintf(stderr, "ggml_hip_mul_mat: unsupported operands (need contiguous Q4_0 or Q8_0 x F32 -> F32, K %% 64 == 0, "
-                        "or Q6_K, Q5_K (Q4_K with GGML_HIP_Q4_K=1) x F32 -> F32, K %% 256 == 0)\n");
+                        "or Q6_K, Q5_K, Q3_K, Q2_K (Q4_K with GGML_HIP_Q4_K=1) x F32 -> F32, K %% 256 == 0)\n");
         abort();
     }
     const int64_t K = src0->ne[0], M = src0->ne[1], N = src1->ne[1];

@@ -16,7 +16,7 @@ constexpr int MAX_OPT = 4;    // GGML_MAX_OPT   ggml.h:200
 constexpr int MAX_NAME = 48;  // GGML_MAX_NAME  ggml.h:201
 
 enum type : int { TYPE_F32 = 0, TYPE_F16 = 1, TYPE_Q4_0 = 2, TYPE_Q4_1 = 3, TYPE_Q5_0 = 6, TYPE_Q5_1 = 7, TYPE_Q8_0 = 8,
-                  TYPE_Q4_K = 12, TYPE_Q5_K = 13, TYPE_Q6_K = 14, TYPE_I32 = 18, TYPE_COUNT = 19 };
+                  TYPE_Q2_K = 10, TYPE_Q3_K = 11, TYPE_Q4_K = 12, TYPE_Q5_K = 13, TYPE_Q6_K = 14, TYPE_I32 = 18, TYPE_COUNT = 19 };
 enum backend : int { BACKEND_CPU = 0, BACKEND_GPU = 10, BACKEND_GPU_SPLIT = 20 };   // ggml.h:257-261
 // enum ggml_op (ggml.h:274-350, with the fork's GGML_OP_EXT_* at 28-31; tests/golden/ggml_op_enum.json)
 enum op : int { OP_NONE = 0, OP_ADD = 2, OP_MUL = 6, OP_SILU = 23, OP_RMS_NORM = 26, OP_MUL_MAT = 32, OP_SCALE = 34,

@@ -194,6 +194,20 @@ hipError_t quantize_q8_K_digit_planes(const float *x, int64_t K, int64_t N, void
 hipError_t gemm_q45_K(bool qh, const void *W, int64_t K, int64_t M, const void *xqs, const float *xd, const void *xdig,
                       int64_t N, float *y, int64_t ldy, const DeviceInfo &dev, hipStream_t s);
 
+// Q3_K / Q2_K (q23_k.hip): the layer matrices of a "mostly Q3_K" / "mostly Q2_K" file.  W: ggml block_q3_K (110 bytes
+// per 256 weights) or block_q2_K (84 bytes) rows, verbatim, the matrix 4-byte aligned (a Q3_K block is then only
+// 2-byte aligned; no byte outside the matrix is read); q3: true Q3_K, false Q2_K.
+constexpr int Q3KB = 110;     // sizeof(block_q3_K)
+constexpr int Q2KB = 84;      // sizeof(block_q2_K)
+// dequantize_row_q3_K / dequantize_row_q2_K, bit-exact
+hipError_t dequantize_q23_K(bool q3, const void *wq, int64_t K, int64_t M, float *w, hipStream_t s);
+// fused q8_K quantize of x (LDS) + q.q8_K GEMV; K % 256 == 0, K <= 16384; N > 8 runs column tiles of 8
+hipError_t gemv_q23_K(bool q3, const void *W, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
+                      const DeviceInfo &dev, hipStream_t s);
+// exact mode: y bit-identical to the AVX2 ggml_vec_dot_q3_K_q8_K / _q2_K_q8_K on the pre-quantized xq8k; any N
+hipError_t mm_exact_q23_K(bool q3, const void *W, int64_t K, int64_t M, const void *xq8k, int64_t N, float *y,
+                          int64_t ldy, hipStream_t s);
+
 // Q4_1 / Q5_0 / Q5_1 weights (blk32_w.hip): the layer matrices of a "mostly Q4_1 / Q5_0 / Q5_1" file.  W: ggml
 // block_q4_1 (20 bytes per 32 weights), block_q5_0 (22) or block_q5_1 (24) rows, verbatim, 4-byte aligned (K % 64
 // == 0); qh: the type has a fifth bit plane (Q5_0, Q5_1), mn: a minimum and q8_1 activations (Q4_1, Q5_1).

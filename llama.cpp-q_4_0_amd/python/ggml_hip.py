@@ -69,6 +69,11 @@ def _bind(L):
         "ggml_hip_debug_set_q4_K": ([i32], i32),
         "ggml_hip_debug_q45k_auto_algo": ([i32, i64, i64, i64], i32),
         "ggml_hip_debug_set_q45k_gemm_min_n": ([i32], i32),
+        "ggml_hip_dequantize_q3_K": ([vp, i64, i64, vp, vp], i32),
+        "ggml_hip_dequantize_q2_K": ([vp, i64, i64, vp, vp], i32),
+        "ggml_hip_mul_mat_q3_K": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
+        "ggml_hip_mul_mat_q2_K": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
+        "ggml_hip_debug_q23k_auto_algo": ([i32, i64, i64, i64], i32),
         "ggml_hip_debug_q8_0_auto_algo": ([i64, i64, i64], i32),
         "ggml_hip_debug_set_q8_0_gemm_min_n": ([i32], i32),
         "ggml_hip_dequantize_q4_1": ([vp, i64, i64, vp, vp], i32),
@@ -375,6 +380,31 @@ def debug_set_q45k_gemm_min_n(n):
     return load().ggml_hip_debug_set_q45k_gemm_min_n(n)
 
 
+def dequantize_q3_K(wq_dev, K, M, w_dev, stream=None):
+    check(load().ggml_hip_dequantize_q3_K(_ptr(wq_dev), K, M, _ptr(w_dev), stream), "dequantize_q3_K")
+
+
+def dequantize_q2_K(wq_dev, K, M, w_dev, stream=None):
+    check(load().ggml_hip_dequantize_q2_K(_ptr(wq_dev), K, M, _ptr(w_dev), stream), "dequantize_q2_K")
+
+
+def mul_mat_q3_K(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_off=0, x_off=0, y_off=0):
+    """Q3_K rows (110 * K / 256 bytes each, the matrix 4-byte aligned) x f32 [N][K] -> f32 y[n * ldy + m]; algo 0 auto
+    (exact mode or K > 16384: 4; else 1), 1 GEMV (column tiles of 8, K <= 16384), 4 exact.  No GEMM yet."""
+    _mul_mat_typed("mul_mat_q3_K", w_dev, K, M, x_dev, N, y_dev, algo, ldy, stream, w_off, x_off, y_off)
+
+
+def mul_mat_q2_K(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_off=0, x_off=0, y_off=0):
+    """Q2_K rows (84 * K / 256 bytes each, 4-byte aligned) x f32 [N][K] -> f32 y[n * ldy + m]; algos as mul_mat_q3_K."""
+    _mul_mat_typed("mul_mat_q2_K", w_dev, K, M, x_dev, N, y_dev, algo, ldy, stream, w_off, x_off, y_off)
+
+
+def debug_q23k_auto_algo(gtype, K, M, N):
+    """The algo that algo 0 of mul_mat_q3_K / mul_mat_q2_K (gtype = GGML_TYPE_Q3_K / GGML_TYPE_Q2_K) would run now:
+    1 or 4; no device needed."""
+    return load().ggml_hip_debug_q23k_auto_algo(gtype, K, M, N)
+
+
 class ChainTask(ctypes.Structure):
     """struct ggml_hip_chain_task (include/ggml-hip.h)"""
     _fields_ = [("nmat", ctypes.c_int), ("K", ctypes.c_int64), ("x", ctypes.c_void_p),
@@ -490,6 +520,7 @@ GGML_TYPE_Q6_K = 14
 GGML_TYPE_Q8_0 = 8
 GGML_TYPE_Q4_1, GGML_TYPE_Q5_0, GGML_TYPE_Q5_1 = 3, 6, 7
 GGML_TYPE_Q4_K, GGML_TYPE_Q5_K = 12, 13
+GGML_TYPE_Q2_K, GGML_TYPE_Q3_K = 10, 11
 GGML_BACKEND_CPU, GGML_BACKEND_GPU, GGML_BACKEND_GPU_SPLIT = 0, 10, 20
 GGML_OP_MUL_MAT = 32
 GGML_TASK_INIT, GGML_TASK_COMPUTE, GGML_TASK_FINALIZE = 0, 1, 2
@@ -538,6 +569,9 @@ def make_tensor(gtype, ne, data=None, backend=GGML_BACKEND_CPU):
         t.nb[1] = t.nb[0] * ne[0] // 32
     elif gtype in (GGML_TYPE_Q5_K, GGML_TYPE_Q4_K):
         t.nb[0] = 176 if gtype == GGML_TYPE_Q5_K else 144
+        t.nb[1] = t.nb[0] * ne[0] // 256
+    elif gtype in (GGML_TYPE_Q3_K, GGML_TYPE_Q2_K):
+        t.nb[0] = 110 if gtype == GGML_TYPE_Q3_K else 84
         t.nb[1] = t.nb[0] * ne[0] // 256
     else:
         t.nb[0] = 4
