@@ -284,19 +284,27 @@ int ggml_hip_debug_set_q4_K(int on);
  * dequantize_q3_K / _q2_K: dequantize_row_q3_K (k_quants.c:531-579) / dequantize_row_q2_K (352-396), bit-exact. */
 int ggml_hip_dequantize_q3_K(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream);
 int ggml_hip_dequantize_q2_K(const void *dev_wq, int64_t K, int64_t M, float *dev_w, void *stream);
-/* y[n * ldy + m], ldy >= M.  algo: 0 auto (4 in exact mode and for K > 16384; else 1), 1 GEMV (K <= 16384) with the
- * q8_K quantization of x fused in, exact int32 superblock sums and one fixed fp32 order per superblock (column
+/* y[n * ldy + m], ldy >= M.  algo: 0 auto (4 in exact mode and for K > 16384; else 8 when N >= the GEMM threshold,
+ * which is "never" unless set; else 1), 1 GEMV (K <= 16384) with the q8_K quantization of x fused in, exact int32 superblock sums and one fixed fp32 order per superblock (column
  * tiles of 8 for N > 8, bitwise the per-tile calls; y does not depend on the launch geometry), 4 exact:
  * bit-identical to the AVX2 branch of ggml_vec_dot_q3_K_q8_K (k_quants.c:1836-1938) / ggml_vec_dot_q2_K_q8_K
- * (1330-1394).  There is no prefill GEMM for these types yet: prefill runs as column tiles of the GEMV.  Anything
- * else (2, 3, 5, 6 and 7 included) -> GGML_HIP_ERR_INVALID. */
+ * (1330-1394), 8 prefill GEMM on the int8 matrix cores (any K % 256 == 0): the blocks read in place, the scale
+ * folded into the int8 weight, x quantized to q8_K into the workspace (covered by ggml_hip_reserve_workspace(K, N));
+ * every y bit for bit algo 1's (the same exact integer superblock sums and the same fp32 step per superblock, in
+ * order), so the auto switch between 1 and 8 never changes a result.  Anything else (2, 3, 5, 6 and 7 included) ->
+ * GGML_HIP_ERR_INVALID. */
 int ggml_hip_mul_mat_q3_K(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N,
                           float *dev_y, int64_t ldy, int algo, void *stream);
 int ggml_hip_mul_mat_q2_K(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N,
                           float *dev_y, int64_t ldy, int algo, void *stream);
 /* debug, no device needed: the algo that algo 0 of ggml_hip_mul_mat_q3_K / _q2_K (type = GGML_TYPE_Q3_K 11 /
- * GGML_TYPE_Q2_K 10) would run now: 1 or 4; a bad type or K -> GGML_HIP_ERR_INVALID */
+ * GGML_TYPE_Q2_K 10) would run now: 1, 4 or 8; a bad type or K -> GGML_HIP_ERR_INVALID */
 int ggml_hip_debug_q23k_auto_algo(int type, int64_t K, int64_t M, int64_t N);
+/* debug: the smallest N at which auto takes the Q3_K / Q2_K GEMM (algo 8), one value for both types.  Default
+ * INT_MAX: never, auto runs the GEMV at every N; GGML_HIP_Q23K_GEMM_MIN_N switches it on (the measured crossover is
+ * in DESIGN.md section 4b); values below 9 count as 9; -1 restores the environment value or the default.  Returns
+ * the previous value. */
+int ggml_hip_debug_set_q23k_gemm_min_n(int n);
 
 /* Sibling mul_mats that share the activation x (ggml graphs issue wq/wk/wv and w1/w3 on the same
  * src1): n <= 4 weight matrices of the same K, y_i = W_i x with y_i f32 [N][M_i].  One launch for

@@ -218,6 +218,8 @@ int ggml_hip_debug_q23k_auto_algo(int type, int64_t K, int64_t M, int64_t N) {
     return debug_auto_algo(type, K, M, N);
 }
 
+int ggml_hip_debug_set_q23k_gemm_min_n(int n) { return weight_type(gabi::TYPE_Q3_K)->min_n->set(n); }
+
 /* not in the public header: force the Q8_0 GEMV's launch policy (tests: every policy gives the same y bitwise) */
 int ggml_hip_debug_set_q8_0_gemv_policy(int map, int depth, int wg_per_cu) {
     ghip::gemv_q8_0w_set_policy(map, depth, wg_per_cu);

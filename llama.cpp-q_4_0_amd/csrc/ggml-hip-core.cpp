@@ -343,9 +343,9 @@ static GemmMinN g_q5_0_min_n{"GGML_HIP_Q5_0_GEMM_MIN_N", 32};
 // Q4_1 / Q5_1 (algo 7, q5x_gemm.hip): "never" by default, so auto runs the GEMV at every N until the user sets the
 // threshold (the measured crossover is in DESIGN §4b; tools/q5x_bench.py, profiles/q5x1_gemm.json)
 static GemmMinN g_q41_q51_min_n{"GGML_HIP_Q41_Q51_GEMM_MIN_N", INT_MAX};
-// Q3_K / Q2_K have no GEMM yet: their rows name the GEMV behind a threshold that is "never", so auto runs
-// the GEMV's column tiles at every N and auto_algo stays one expression (the variable is reserved for that GEMM:
-// until it exists both sides of the threshold are algo 1, so setting it changes nothing)
+// Q3_K / Q2_K (algo 8, q23_k_gemm.hip): "never" by default, so auto runs the GEMV's column tiles at every N until the
+// user sets the threshold (the measured crossover is in DESIGN §4b; tools/q23k_gemm_bench.py,
+// profiles/q23k_gemm.json).  The GEMM's y is the GEMV's bit for bit, so setting it never changes a result.
 static GemmMinN g_q23k_min_n{"GGML_HIP_Q23K_GEMM_MIN_N", INT_MAX};
 
 // the K a type's GEMV takes: one token's q8_K image in the LDS for the k-quants (w2 of a 30B / 65B model has K =
@@ -391,19 +391,19 @@ static const WeightType ROW_Q4_K = {
     QK_K, 16, ERR_DQ_Q45K};
 
 // Q3_K / Q2_K (q23_k.hip): the matrix 4-byte aligned, which leaves a Q3_K block (110 bytes) at 0 or 2 mod 4; the
-// kernels read no byte outside the matrix.  No GEMM: algo 1 behind the "never" threshold, the exact kernel where the
-// GEMV cannot take K.
+// kernels read no byte outside the matrix.  The GEMM (algo 8) sits behind a threshold whose default is "never"; the
+// exact kernel where the GEMV cannot take K.
 static constexpr const char *ERR_ALIGN_Q23K = "W must be 4-byte, x 16-byte, y 4-byte aligned";
 static constexpr const char *ERR_GEMV_Q23K = "the Q3_K / Q2_K GEMV supports K <= 16384";
 static constexpr const char *ERR_DQ_Q23K = "w must be 16-byte aligned, the Q3_K / Q2_K rows 2-byte aligned";
 static const WeightType ROW_Q3_K = {
     QK_K, 4, (int64_t)1 << 31,
-    1, 4, &g_q23k_min_n, gemv_takes_k_kquant, mul_mat_q3k_dev,
+    8, 4, &g_q23k_min_n, gemv_takes_k_kquant, mul_mat_q3k_dev,
     ERR_K256, ERR_ALIGN_Q23K, ERR_GEMV_Q23K,
     QK_K, 2, ERR_DQ_Q23K};
 static const WeightType ROW_Q2_K = {
     QK_K, 4, (int64_t)1 << 31,
-    1, 4, &g_q23k_min_n, gemv_takes_k_kquant, mul_mat_q2k_dev,
+    8, 4, &g_q23k_min_n, gemv_takes_k_kquant, mul_mat_q2k_dev,
     ERR_K256, ERR_ALIGN_Q23K, ERR_GEMV_Q23K,
     QK_K, 2, ERR_DQ_Q23K};
 
@@ -467,7 +467,8 @@ int check_operands(const WeightType &t, const void *w, int64_t K, int64_t M, con
     return GGML_HIP_OK;
 }
 
-// the workspaces of the k-quant arms.  Exact: x as q8_K blocks.  Q6_K GEMM: qs int8 [N][K] + d f32 [N][K / 256].
+// the workspaces of the k-quant arms.  Exact: x as q8_K blocks.  Q6_K and Q3_K / Q2_K GEMM: qs int8 [N][K] + d f32
+// [N][K / 256].
 // Q5_K / Q4_K GEMM: qs int8 [N][K] + dig int8 [N][K / 256][16] + d f32 [N][K / 256], 256 + 20 bytes per 256 elements
 // against the 288 of workspace_bytes(K, N) behind the same padding of qs.  None is more than workspace_bytes(K, N),
 // which ggml_hip_reserve_workspace reserves.
@@ -630,11 +631,12 @@ static int mul_mat_q4k_dev(const void *w, int64_t K, int64_t M, const float *x, 
     return mul_mat_q45k_dev(false, w, K, M, x, N, y, ldy, algo, s);
 }
 
-// Q3_K (q3) / Q2_K (q23_k.hip): the GEMV and the exact kernel only.  An algo the types reject is refused before
-// anything else, an empty call included.
+// Q3_K (q3) / Q2_K (q23_k.hip, q23_k_gemm.hip): algo 8 = the q8_K values of x as planes in the workspace (the Q6_K
+// GEMM's quantizer and layout) + k_gemm_q23_K on the weights in place, any K % 256 == 0.  An algo the types reject is
+// refused before anything else, an empty call included.
 static int mul_mat_q23k_dev(bool q3, const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
                             int algo, hipStream_t s) {
-    if (algo != 0 && algo != 1 && algo != 4) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1 or 4");
+    if (algo != 0 && algo != 1 && algo != 4 && algo != 8) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1, 4 or 8");
     const WeightType &t = ROW_Q3_K;                      // (the two rows differ in the run function only)
     const int rc = check_operands(t, w, K, M, x, N, y, ldy);
     if (rc != GGML_HIP_OK || N == 0) return rc;
@@ -646,6 +648,15 @@ static int mul_mat_q23k_dev(bool q3, const void *w, int64_t K, int64_t M, const 
         return GGML_HIP_OK;
     }
     void *ws = nullptr;
+    if (algo == 8) {
+        if (too_many_tiles(M, N)) return fail(GGML_HIP_ERR_UNSUPPORTED, ERR_TILES);
+        const int wrc = stream_workspace(id, s, workspace_bytes_q6k_gemm(K, N), &ws);
+        if (wrc != GGML_HIP_OK) return wrc;
+        float *xd = (float *)((char *)ws + kquant_planes_offset(K, N));
+        HIP_RET(ghip::quantize_q8_K_planes(x, K, N, ws, xd, s));
+        HIP_RET(ghip::gemm_q23_K(q3, w, K, M, ws, xd, N, y, ldy, g_dev[id].info, s));
+        return GGML_HIP_OK;
+    }
     const int wrc = quantize_q8k_ws(id, x, K, N, s, &ws);
     if (wrc != GGML_HIP_OK) return wrc;
     HIP_RET(ghip::mm_exact_q23_K(q3, w, K, M, ws, N, y, ldy, s));

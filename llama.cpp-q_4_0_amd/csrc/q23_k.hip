@@ -1,6 +1,6 @@
 // q23_k.hip — the Q3_K / Q2_K x F32 mul_mat of a "mostly Q3_K" / "mostly Q2_K" file's layer matrices (gfx950,
 // wave64): the dequantizer, the fused GEMV (N <= 8 per launch) and the exact kernel, one template parameter Q3
-// (true: Q3_K, false: Q2_K); there is no prefill GEMM for these types yet.  Shared device helpers:
+// (true: Q3_K, false: Q2_K); the prefill GEMM, bitwise this GEMV, is q23_k_gemm.hip.  Shared device helpers:
 // q4_0_device.h, q6_k_device.h (q8k_block_lane), q23_k_device.h (Q23<Q3>, q23_values, the scales).  What each
 // kernel restates (reference = k_quants.c of Fcucgvhhhvjv/llama.cpp-q_4_0, QK_K = 256):
 //   k_dequantize_q23_K<Q3>  dequantize_row_q3_K k_quants.c:531-579 / dequantize_row_q2_K 352-396 (bit-exact)

@@ -207,6 +207,10 @@ hipError_t gemv_q23_K(bool q3, const void *W, int64_t K, int64_t M, const float 
 // exact mode: y bit-identical to the AVX2 ggml_vec_dot_q3_K_q8_K / _q2_K_q8_K on the pre-quantized xq8k; any N
 hipError_t mm_exact_q23_K(bool q3, const void *W, int64_t K, int64_t M, const void *xq8k, int64_t N, float *y,
                           int64_t ldy, hipStream_t s);
+// prefill (q23_k_gemm.hip): the int8-MFMA GEMM on the planes of quantize_q8_K_planes, the blocks read in place, y
+// bitwise gemv_q23_K's; any K % 256 == 0 (N K < 2^31), M, N >= 1
+hipError_t gemm_q23_K(bool q3, const void *W, int64_t K, int64_t M, const void *xqs, const float *xd, int64_t N, float *y,
+                      int64_t ldy, const DeviceInfo &dev, hipStream_t s);
 
 // Q4_1 / Q5_0 / Q5_1 weights (blk32_w.hip): the layer matrices of a "mostly Q4_1 / Q5_0 / Q5_1" file.  W: ggml
 // block_q4_1 (20 bytes per 32 weights), block_q5_0 (22) or block_q5_1 (24) rows, verbatim, 4-byte aligned (K % 64

@@ -74,6 +74,7 @@ def _bind(L):
         "ggml_hip_mul_mat_q3_K": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
         "ggml_hip_mul_mat_q2_K": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
         "ggml_hip_debug_q23k_auto_algo": ([i32, i64, i64, i64], i32),
+        "ggml_hip_debug_set_q23k_gemm_min_n": ([i32], i32),
         "ggml_hip_debug_q8_0_auto_algo": ([i64, i64, i64], i32),
         "ggml_hip_debug_set_q8_0_gemm_min_n": ([i32], i32),
         "ggml_hip_dequantize_q4_1": ([vp, i64, i64, vp, vp], i32),
@@ -390,7 +391,8 @@ def dequantize_q2_K(wq_dev, K, M, w_dev, stream=None):
 
 def mul_mat_q3_K(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_off=0, x_off=0, y_off=0):
     """Q3_K rows (110 * K / 256 bytes each, the matrix 4-byte aligned) x f32 [N][K] -> f32 y[n * ldy + m]; algo 0 auto
-    (exact mode or K > 16384: 4; else 1), 1 GEMV (column tiles of 8, K <= 16384), 4 exact.  No GEMM yet."""
+    (exact mode or K > 16384: 4; N below the GEMM threshold, "never" unless set: 1; else 8), 1 GEMV (column tiles of
+    8, K <= 16384), 4 exact, 8 int8-MFMA GEMM (bitwise algo 1)."""
     _mul_mat_typed("mul_mat_q3_K", w_dev, K, M, x_dev, N, y_dev, algo, ldy, stream, w_off, x_off, y_off)
 
 
@@ -401,8 +403,14 @@ def mul_mat_q2_K(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_
 
 def debug_q23k_auto_algo(gtype, K, M, N):
     """The algo that algo 0 of mul_mat_q3_K / mul_mat_q2_K (gtype = GGML_TYPE_Q3_K / GGML_TYPE_Q2_K) would run now:
-    1 or 4; no device needed."""
+    1, 4 or 8; no device needed."""
     return load().ggml_hip_debug_q23k_auto_algo(gtype, K, M, N)
+
+
+def debug_set_q23k_gemm_min_n(n):
+    """The smallest N at which auto takes the Q3_K / Q2_K GEMM (default: never; below 9 counts as 9; -1: the
+    environment value or the default); returns the previous value."""
+    return load().ggml_hip_debug_set_q23k_gemm_min_n(n)
 
 
 class ChainTask(ctypes.Structure):
