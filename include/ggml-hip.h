@@ -15,7 +15,9 @@
  * matrices of a "mostly Q5_K" file (ggml_vec_dot_q5_K_q8_K semantics), and with
  * src0 = GGML_TYPE_Q3_K / GGML_TYPE_Q2_K: the layer matrices of the "mostly
  * Q3_K" and "mostly Q2_K" files (ggml_vec_dot_q3_K_q8_K / _q2_K_q8_K semantics),
- * and with src0 = GGML_TYPE_Q4_1 / Q5_0 / Q5_1.
+ * and with src0 = GGML_TYPE_Q4_1 / Q5_0 / Q5_1, and with src0 = a 2-D
+ * GGML_TYPE_F16 leaf: the matrices of a "mostly F16" file
+ * (ggml_compute_forward_mul_mat_f16_f32 semantics).
  * src0 = GGML_TYPE_Q4_K (a "mostly Q4_K" file) is taken on this hook path only
  * with GGML_HIP_Q4_K=1 / ggml_hip_debug_set_q4_K(1) (off by default);
  * the tensor-free ggml_hip_mul_mat_q4_K always runs.  Everything
@@ -305,6 +307,27 @@ int ggml_hip_debug_q23k_auto_algo(int type, int64_t K, int64_t M, int64_t N);
  * in DESIGN.md section 4b); values below 9 count as 9; -1 restores the environment value or the default.  Returns
  * the previous value. */
 int ggml_hip_debug_set_q23k_gemm_min_n(int n);
+/* F16 WEIGHTS (contiguous rows of K halves; dev_w 16-byte aligned, K % 32 == 0: the matrices of a "mostly F16" file)
+ * x F32 -> F32 with the semantics of ggml_compute_forward_mul_mat_f16_f32 (ggml.c:11026): x is rounded to fp16
+ * (round to nearest even) and every product of two fp16 values is exact in fp32.  y[n * ldy + m], ldy >= M.
+ * Stream-ordered and capturable; no workspace.  No byte outside [dev_w, dev_w + M * K * 2) is read.  Status codes as
+ * for the q4_0 entry points; N == 0 is a no-op.  algo: 0 auto (4 in exact mode and for a K the GEMV cannot take; else
+ * 9 when N >= the GEMM threshold; else 1), 1 GEMV (K <= 65536) with the fp16 rounding of x fused in and one fixed
+ * order of the fp32 additions per K (csrc/f16_w.hip, restated in tests/f16w_ref.py; column tiles of at most 8 above
+ * that, bitwise the per-tile calls; y does not depend on N, M or the launch geometry) — within the fp32-accumulation
+ * bound of the reference, 4 exact: bit-identical to ggml_vec_dot_f16 in its AVX2 / F16C schedule (the kernels of
+ * the attention's F16 x F32 products, ldy == M only), 9 prefill GEMM on the f16 matrix cores (the attention's
+ * fast-mode kernel, ldy == M only; within the same bound).  Anything else (2, 3, 5, 6, 7 and 8 included) ->
+ * GGML_HIP_ERR_INVALID, before anything else is checked; 4 or 9 with ldy != M -> GGML_HIP_ERR_UNSUPPORTED. */
+int ggml_hip_mul_mat_f16(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N,
+                         float *dev_y, int64_t ldy, int algo, void *stream);
+/* debug, no device needed: the algo that algo 0 of ggml_hip_mul_mat_f16 would run now: 1, 4 or 9; a bad K ->
+ * GGML_HIP_ERR_INVALID */
+int ggml_hip_debug_f16w_auto_algo(int64_t K, int64_t M, int64_t N);
+/* debug: the smallest N at which auto takes the F16 GEMM (algo 9).  Default 32 (GGML_HIP_F16W_GEMM_MIN_N; the
+ * measured rows are in DESIGN.md section 4b); values below 9 count as 9; -1 restores the environment value or the
+ * default.  Returns the previous value. */
+int ggml_hip_debug_set_f16w_gemm_min_n(int n);
 
 /* Sibling mul_mats that share the activation x (ggml graphs issue wq/wk/wv and w1/w3 on the same
  * src1): n <= 4 weight matrices of the same K, y_i = W_i x with y_i f32 [N][M_i].  One launch for

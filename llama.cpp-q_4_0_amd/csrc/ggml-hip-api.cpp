@@ -220,6 +220,16 @@ int ggml_hip_debug_q23k_auto_algo(int type, int64_t K, int64_t M, int64_t N) {
 
 int ggml_hip_debug_set_q23k_gemm_min_n(int n) { return weight_type(gabi::TYPE_Q3_K)->min_n->set(n); }
 
+// F16 weights (f16_w.hip; algo 4 and 9 are ggml_ops.hip's F16 x F32 kernels)
+int ggml_hip_mul_mat_f16(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N, float *dev_y,
+                         int64_t ldy, int algo, void *stream) {
+    return mul_mat_type(gabi::TYPE_F16, dev_w, K, M, dev_x, N, dev_y, ldy, algo, stream);
+}
+
+int ggml_hip_debug_f16w_auto_algo(int64_t K, int64_t M, int64_t N) { return debug_auto_algo(gabi::TYPE_F16, K, M, N); }
+
+int ggml_hip_debug_set_f16w_gemm_min_n(int n) { return weight_type(gabi::TYPE_F16)->min_n->set(n); }
+
 /* not in the public header: force the Q8_0 GEMV's launch policy (tests: every policy gives the same y bitwise) */
 int ggml_hip_debug_set_q8_0_gemv_policy(int map, int depth, int wg_per_cu) {
     ghip::gemv_q8_0w_set_policy(map, depth, wg_per_cu);

@@ -347,16 +347,26 @@ static GemmMinN g_q41_q51_min_n{"GGML_HIP_Q41_Q51_GEMM_MIN_N", INT_MAX};
 // user sets the threshold (the measured crossover is in DESIGN §4b; tools/q23k_gemm_bench.py,
 // profiles/q23k_gemm.json).  The GEMM's y is the GEMV's bit for bit, so setting it never changes a result.
 static GemmMinN g_q23k_min_n{"GGML_HIP_Q23K_GEMM_MIN_N", INT_MAX};
+// F16 (algo 9 = k_mul_mat_f16_f32_mfma, the attention's fast-mode kernel): 32, the N at which an F16 src0 took that
+// kernel before the GEMV existed (GGML_HIP_F16_MFMA_MIN's default).  Measured (tools/f16w_bench.py,
+// profiles/f16w_gemm.json; weights from HBM; tiled GEMV against the MFMA kernel, us): 4096 -> 4096 N = 32 47.4 / 93.9,
+// N = 64 92.3 / 94.5, N = 128 182.7 / 93.3; 4096 -> 11008 N = 16 52.0 / 95.2, N = 32 103.2 / 97.3, N = 64 203.7 /
+// 98.6; 11008 -> 4096 N = 32 143.6 / 250.5, N = 64 273.4 / 252.3.  The crossover is at 128 / 32 / 64: it is not away
+// from 32 on all three shapes, so the default stays 32.  The MFMA kernel, built for K = 128, is flat in N at ~93 / 97 /
+// 250 us up to N = 512 (0.36 / 0.93 / 0.36 TB/s of weight bytes): a weight-shaped F16 GEMM is DESIGN §8's.
+static GemmMinN g_f16w_min_n{"GGML_HIP_F16W_GEMM_MIN_N", 32};
 
 // the K a type's GEMV takes: one token's q8_K image in the LDS for the k-quants (w2 of a 30B / 65B model has K =
 // 17920 / 22016), one token's q8_0 for Q8_0
 static bool gemv_takes_k_kquant(int64_t K) { return K <= 16384; }
 static bool gemv_takes_k_q8_0(int64_t K) { return ghip::gemv_q8_0w_max_tokens(K) >= 1; }
 static bool gemv_takes_k_q5x(int64_t K) { return ghip::gemv_q5x_max_tokens(K) >= 1; }
+static bool gemv_takes_k_f16w(int64_t K) { return ghip::gemv_f16w_max_tokens(K) >= 1; }
 
 static MulMatSig mul_mat_q6k_dev, mul_mat_q8_0_dev, mul_mat_q5k_dev, mul_mat_q4k_dev;
 static MulMatSig mul_mat_q4_1_dev, mul_mat_q5_0_dev, mul_mat_q5_1_dev;
 static MulMatSig mul_mat_q3k_dev, mul_mat_q2k_dev;
+static MulMatSig mul_mat_f16w_dev;
 
 static constexpr const char *ERR_K256 = "K must be a multiple of 256 (QK_K)";
 static constexpr const char *ERR_ALIGN_Q45K = "W and x must be 16-byte, y 4-byte aligned";
@@ -433,8 +443,19 @@ static const WeightType ROW_Q5_1 = {
     ERR_K64_Q5X, ERR_ALIGN_Q5X, ERR_GEMV_Q5X,
     64, 4, ERR_DQ_Q5X};
 
+// F16 (f16_w.hip; the "mostly F16" files): contiguous rows of K halves, 16-byte aligned, K % 32 == 0 (the reference's
+// GGML_CUDA_DMMV_X).  There is nothing to dequantize and no kernel of its own beside the GEMV: exact mode (algo 4) and
+// the GEMM (algo 9) are the attention's F16 x F32 kernels (ggml_ops.hip) on contiguous strides, unchanged.  The exact
+// kernels where the GEMV cannot take K.
+static const WeightType ROW_F16 = {
+    32, 16, (int64_t)1 << 31,
+    9, 4, &g_f16w_min_n, gemv_takes_k_f16w, mul_mat_f16w_dev,
+    "K must be a multiple of 32", "W and x must be 16-byte, y 4-byte aligned", "K too long for the F16 GEMV",
+    32, 16, "F16 rows are not dequantized"};
+
 const WeightType *weight_type(int type) {
     switch (type) {
+        case gabi::TYPE_F16: return &ROW_F16;
         case gabi::TYPE_Q4_1: return &ROW_Q4_1;
         case gabi::TYPE_Q5_0: return &ROW_Q5_0;
         case gabi::TYPE_Q5_1: return &ROW_Q5_1;
@@ -671,6 +692,29 @@ static int mul_mat_q2k_dev(const void *w, int64_t K, int64_t M, const float *x, 
     return mul_mat_q23k_dev(false, w, K, M, x, N, y, ldy, algo, s);
 }
 
+// F16 (f16_w.hip, ggml_ops.hip): algo 1 = k_gemv_f16w in column tiles; algo 4 = op_mul_mat_f16_f32's bitwise kernels
+// (ggml_vec_dot_f16 in its AVX2 / F16C schedule) and algo 9 = its MFMA kernel, both on contiguous strides.  Those
+// launchers write y as [N][M] with no row pitch, so 4 and 9 take ldy == M only (the hook never passes another).  An
+// algo the type rejects is refused before anything else, an empty call included.
+static int mul_mat_f16w_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                            hipStream_t s) {
+    if (algo != 0 && algo != 1 && algo != 4 && algo != 9) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1, 4 or 9");
+    const WeightType &t = ROW_F16;
+    const int rc = check_operands(t, w, K, M, x, N, y, ldy);
+    if (rc != GGML_HIP_OK || N == 0) return rc;
+    const int id = current_device();
+    if (algo == 0) algo = auto_algo(t, K, N);
+    if (algo == 1) {
+        if (!t.gemv_takes_k(K)) return fail(GGML_HIP_ERR_UNSUPPORTED, t.err_gemv_k);
+        HIP_RET(ghip::gemv_f16w(w, K, M, x, N, y, ldy, g_dev[id].info, s));
+        return GGML_HIP_OK;
+    }
+    if (ldy != M) return fail(GGML_HIP_ERR_UNSUPPORTED, "the exact and MFMA F16 kernels (algo 4, 9) need ldy == M");
+    HIP_RET(ghip::op_mul_mat_f16_f32(w, x, y, (int)K, M, N, 1, K * 2, M * K * 2, K * 4, N * K * 4, s, nullptr,
+                                     algo == 4 ? -1 : 2));
+    return GGML_HIP_OK;
+}
+
 // Sibling matrices (one x) that all take k_gemm9 on a registered fp6 image: ONE launch over their
 // row tiles (the x image built once, as before).  The launch plans its tiles (128 x 128 / 128 x 64 /
 // mixed, half tiles) from its own total tile count, which can differ from the per-matrix launches'
@@ -771,12 +815,19 @@ int q4k_set_enabled(int on) {
 // host-resident Q4_K tensor as a type no device op reads; a Q4_K weight that transform_tensor uploaded while the
 // switch was on keeps being served after it is turned off: its data is on the device, so ggml's CPU op could not
 // read it.
+bool f16_weight(const tensor *t) {
+    return t && t->type == gabi::TYPE_F16 && t->op == gabi::OP_NONE && t->ne[2] == 1 && t->ne[3] == 1 && t->ne[0] > 0 &&
+           t->ne[0] % ROW_F16.k_granule == 0 && is_contiguous(t);
+}
 bool hook_takes_type(int type) {
     return type == gabi::TYPE_Q4_0 || (weight_type(type) && (type != gabi::TYPE_Q4_K || q4k_enabled()));
 }
 int hook_weight_type(const tensor *src0, const tensor *src1, const tensor *dst) {
     if (supported_mul_mat(src0, src1, dst)) return gabi::TYPE_Q4_0;
     if (!src0 || !supported_mul_mat_type(src0->type, src0, src1, dst)) return gabi::TYPE_COUNT;
+    // an F16 src0 is a weight only as a 2-D leaf: the K and V views of the attention (permuted, transposed, 3-D, never
+    // leaves) keep the F16 x F32 device op and its fusions
+    if (src0->type == gabi::TYPE_F16 && !f16_weight(src0)) return gabi::TYPE_COUNT;
     if (src0->type == gabi::TYPE_Q4_K && !q4k_enabled() && !(on_device(src0) && src0->extra)) return gabi::TYPE_COUNT;
     return src0->type;
 }

@@ -196,6 +196,12 @@ NormChain g_norm;
 void mul_mat_node(const tensor *src0, const tensor *src1, tensor *dst);
 
 char *dptr(const tensor *t) { return (char *)((ggml_tensor_extra_gpu *)t->extra)->data_device[g_main_device]; }
+// an F16 x F32 mul_mat of the attention (a K or V view): every F16 src0 that is no weight matrix (hook_weight_type);
+// an F16 weight's node is an ordinary weight mul_mat: one launch, held for nothing
+bool attn_f16_mm(const tensor *t) {
+    return t->op == gabi::OP_MUL_MAT && t->src0 && t->src0->type == gabi::TYPE_F16 &&
+           hook_weight_type(t->src0, t->src1, t) != gabi::TYPE_F16;
+}
 bool dev_f32(const tensor *t) {
     return t && t->backend == gabi::BACKEND_GPU && t->type == gabi::TYPE_F32 && t->extra && is_contiguous(t);
 }
@@ -224,7 +230,7 @@ bool deferrable(const tensor *t) {
             return dev_f32(t->src0) && same_shape(t, t->src0) && t->ne[3] == 1 && host_scalar_param(t->src1) &&
                    ((const int32_t *)t->src1->data)[2] == 0;
         case gabi::OP_MUL_MAT:       // f16 x f32 (attention): the consumer may be the KQV merge copy
-            return t->src0 && t->src0->type == gabi::TYPE_F16 && t->src0->backend == gabi::BACKEND_GPU && t->src1 &&
+            return attn_f16_mm(t) && t->src0->backend == gabi::BACKEND_GPU && t->src1 &&
                    t->src1->type == gabi::TYPE_F32 && t->src1->backend == gabi::BACKEND_GPU && t->src1->extra;
         default:
             return false;
@@ -277,7 +283,7 @@ bool x9_chain_ok(int64_t ncols, int64_t nrows) {
 // a decode KQ that op_kq_softmax_kqv can compute: K (f16, element stride 2) and q (f32, contiguous head
 // rows) on the device, one query row per head, head dimension <= 256, a contiguous [nkv][1][heads] output
 bool kq_holdable(const tensor *t) {
-    if (!fuse_enabled() || !kq_fold_enabled() || t->op != gabi::OP_MUL_MAT || !dev_f32(t)) return false;
+    if (!fuse_enabled() || !kq_fold_enabled() || !attn_f16_mm(t) || !dev_f32(t)) return false;
     const tensor *K = t->src0, *Q = t->src1;
     return K && Q && K->type == gabi::TYPE_F16 && K->backend == gabi::BACKEND_GPU && K->extra && Q->type == gabi::TYPE_F32 &&
            Q->backend == gabi::BACKEND_GPU && Q->extra && K->nb[0] == 2 && Q->nb[0] == 4 && K->ne[3] == 1 && Q->ne[3] == 1 &&
@@ -369,9 +375,9 @@ bool try_fuse(tensor *t) {
         return true;
     }
     // soft_max chain -> KQV (f16 V^T . softmax, one query row per head): extend
-    if (p.n == 3 && softmax_chain(p) && t->op == gabi::OP_MUL_MAT && same_tensor(t->src1, last) && t->src0 &&
-        t->src0->type == gabi::TYPE_F16 && t->src0->backend == gabi::BACKEND_GPU && t->src0->extra &&
-        t->src0->nb[0] == 2 && t->src0->ne[3] == 1 && last->ne[1] == 1 && last->ne[3] == 1 &&
+    if (p.n == 3 && softmax_chain(p) && attn_f16_mm(t) && same_tensor(t->src1, last) &&
+        t->src0->backend == gabi::BACKEND_GPU && t->src0->extra && t->src0->nb[0] == 2 && t->src0->ne[3] == 1 &&
+        last->ne[1] == 1 && last->ne[3] == 1 &&
         t->src0->ne[0] == last->ne[0] && t->src0->ne[2] == last->ne[2] && last->ne[0] <= 16384 && dev_f32(t) &&
         t->ne[1] == 1 && t->ne[0] == t->src0->ne[1] && dev_f32(p.node[0]->src0)) {
         p.node[p.n++] = hold(t);
@@ -608,7 +614,7 @@ bool group_after_ok(const tensor *t) {
         case gabi::OP_CPY:
             return dev(t->src0) && dev(t->src1);
         case gabi::OP_MUL_MAT:
-            return t->src0 && t->src0->type == gabi::TYPE_F16 && dev(t->src0) && dev(t->src1);
+            return attn_f16_mm(t) && dev(t->src0) && dev(t->src1);
         default:
             return false;
     }
@@ -1064,7 +1070,7 @@ void execute_node(tensor *t) {
         if (trace_nodes())
             fprintf(stderr, "group: %s not joined (mm_ok %d, join_ok %d, after_ok %d)\n", t->name, (int)group_mm_ok(t),
                     group_mm_ok(t) ? (int)group_join_ok(t) : -1, (int)group_after_ok(t));
-        if (!(op == gabi::OP_MUL_MAT && t->src0 && t->src0->type != gabi::TYPE_F16) && group_after_ok(t) &&
+        if (!(op == gabi::OP_MUL_MAT && t->src0 && !attn_f16_mm(t)) && group_after_ok(t) &&
             g_grp.na < 16) {
             g_grp.after[g_grp.na++] = hold(t);
             return;
@@ -1091,7 +1097,7 @@ void execute_node(tensor *t) {
         g_pend.node[g_pend.n++] = hold(t);
         return;
     }
-    if (t->op == gabi::OP_MUL_MAT && t->src0 && t->src0->type != gabi::TYPE_F16) {
+    if (t->op == gabi::OP_MUL_MAT && t->src0 && !attn_f16_mm(t)) {
         count_node(t);
         ggml_hip_mul_mat((const ggml_tensor *)t->src0, (const ggml_tensor *)t->src1, (ggml_tensor *)t);
     } else {

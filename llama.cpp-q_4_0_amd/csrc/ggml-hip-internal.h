@@ -199,6 +199,8 @@ int q4k_set_enabled(int on);                            // returns the previous 
 // the hook path (ggml-hip-tensor.cpp): is `type` a device weight type now / the weight type whose mul_mat this
 // node is, gabi::TYPE_COUNT for none
 bool hook_takes_type(int type);
+// an F16 tensor that is a weight matrix: a contiguous 2-D leaf with K % 32 == 0 (every other F16 src0 is the attention's)
+bool f16_weight(const tensor *t);
 int hook_weight_type(const tensor *src0, const tensor *src1, const tensor *dst);
 // true when ggml_hip_mul_mat_q4_0_multi runs these n siblings at N tokens as ONE k_gemm9 launch on registered
 // fp6 images (mul_mat_group_g9 for n > 1, mul_mat_dev's image GEMM for n = 1); img[i] = the images

@@ -156,8 +156,9 @@ void mul_mat_node(const tensor *src0, const tensor *src1, tensor *dst) {
     const int wtype = hook_weight_type(src0, src1, dst);
     const WeightType *row = weight_type(wtype);          // null: Q4_0
     if (wtype == gabi::TYPE_COUNT) {
-        fprintf(stderr, "ggml_hip_mul_mat: unsupported operands (need contiguous Q4_0 or Q8_0 x F32 -> F32, K %% 64 == 0, "
-                        "or Q6_K, Q5_K, Q3_K, Q2_K (Q4_K with GGML_HIP_Q4_K=1) x F32 -> F32, K %% 256 == 0)\n");
+        fprintf(stderr, "ggml_hip_mul_mat: unsupported operands (need contiguous Q4_0, Q4_1, Q5_0, Q5_1 or Q8_0 x F32 -> F32, "
+                        "K %% 64 == 0, or Q6_K, Q5_K, Q3_K, Q2_K (Q4_K with GGML_HIP_Q4_K=1) x F32 -> F32, K %% 256 == 0, or a "
+                        "2-D F16 leaf x F32 -> F32, K %% 32 == 0)\n");
         abort();
     }
     const int64_t K = src0->ne[0], M = src0->ne[1], N = src1->ne[1];
@@ -368,8 +369,10 @@ void ggml_hip_transform_tensor(void *data, struct ggml_tensor *tensor_) {
         t->extra = nullptr;
         return;
     }
-    if (!hook_takes_type(t->type) && t->backend == gabi::BACKEND_GPU_SPLIT)
-        t->backend = gabi::BACKEND_GPU;   // only the quantized mul_mats read row-split operands
+    // only the weight mul_mats read row-split operands: the quantized types and F16 matrices (f16_weight: the
+    // F16 x F32 device op of every other F16 tensor reads one device buffer)
+    if (t->backend == gabi::BACKEND_GPU_SPLIT && (t->type == gabi::TYPE_F16 ? !f16_weight(t) : !hook_takes_type(t->type)))
+        t->backend = gabi::BACKEND_GPU;
     const int64_t nrows = gabi::nrows(t);
     const size_t nb1 = t->nb[1];
     auto *extra = new ggml_tensor_extra_gpu;
@@ -489,8 +492,9 @@ void ggml_hip_free_scratch(void) {
 bool ggml_hip_compute_forward(struct ggml_compute_params *params_, struct ggml_tensor *tensor_) {
     // ggml-cuda.cu:2933-3021: a node is taken when any operand is device resident (MUL_MAT also when
     // can_mul_mat holds for host operands); only ith == 0 in COMPUTE executes (the other threads
-    // spin in ggml.c:17285-17287).  A quantized mul_mat -> its weight type's kernels (hook_weight_type); F16
-    // mul_mat (attention on the KV cache) and the other ops of a LLaMA layer -> ggml_ops.hip; views are free.
+    // spin in ggml.c:17285-17287).  A weight mul_mat (quantized, or an F16 matrix) -> its weight type's kernels
+    // (hook_weight_type); every other F16 mul_mat (attention on the KV cache) and the other ops of a LLaMA layer ->
+    // ggml_ops.hip; views are free.
     const gabi::compute_params *params = (const gabi::compute_params *)params_;
     tensor *t = (tensor *)tensor_;
     // a host write into cached weights (LoRA apply) invalidates their device copies; INIT runs once per
@@ -503,7 +507,8 @@ bool ggml_hip_compute_forward(struct ggml_compute_params *params_, struct ggml_t
     bool f16_mul_mat = false;
     switch (t->op) {
         case gabi::OP_MUL_MAT:
-            if (t->src0 && t->src0->type == gabi::TYPE_F16) {
+            // an F16 src0 that is no weight (hook_weight_type: the attention's K and V views): the F16 x F32 device op
+            if (t->src0 && t->src0->type == gabi::TYPE_F16 && hook_weight_type(t->src0, t->src1, t) == gabi::TYPE_COUNT) {
                 if (!any_on_device) return false;
                 f16_mul_mat = true;
                 break;

@@ -240,6 +240,14 @@ hipError_t gemm8_prep_w_q5_0(const void *W, int64_t K, int64_t M, void *wws, hip
 hipError_t gemm_q5x1(bool qh, const void *W, int64_t K, int64_t M, const int8_t *xqs, const float *xd, const float *xsum,
                      int64_t N, float *y, int64_t ldy, const DeviceInfo &dev, hipStream_t s);
 
+// ---- F16 weights (f16_w.hip): y[n * ldy + m] = sum_e W[m][e] * fp16(x[n][e]), W contiguous F16 rows (16-byte
+// aligned, K % 32 == 0), one fixed fp32 order per K (tests/f16w_ref.py).  N > gemv_f16w_max_tokens(K) runs column tiles
+// (a column's y does not depend on its tile); max_tokens is 8 up to K = 8192, 5 at K = 11008 and 0 where one token's
+// fp16 image exceeds the LDS (K > 65536)
+int gemv_f16w_max_tokens(int64_t K);
+hipError_t gemv_f16w(const void *W, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
+                     const DeviceInfo &dev, hipStream_t s);
+
 // Multi-GPU helper: y[n*ldy + row0[r] + i] = slab[r][n][i] for i < rows[r] (gather compaction).
 // row_begin travels as a kernel argument (no host->device copy, capture-safe)
 static constexpr int SCATTER_MAX_RANKS = 256;

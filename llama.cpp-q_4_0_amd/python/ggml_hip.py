@@ -90,6 +90,9 @@ def _bind(L):
         "ggml_hip_debug_set_q5_0_gemm_min_n": ([i32], i32),
         "ggml_hip_debug_set_q41_q51_gemm_min_n": ([i32], i32),
         "ggml_hip_debug_set_q5x_gemv_policy": ([i32, i32, i32], i32),
+        "ggml_hip_mul_mat_f16": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
+        "ggml_hip_debug_f16w_auto_algo": ([i64, i64, i64], i32),
+        "ggml_hip_debug_set_f16w_gemm_min_n": ([i32], i32),
         "ggml_hip_reserve_workspace": ([i64, i64], i32),
         "ggml_hip_reserve_workspace_mm": ([i64, i64, i64], i32),
         "ggml_hip_weight_image_create": ([vp, i64, i64, vp], i32),
@@ -348,6 +351,13 @@ def mul_mat_q5_1(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_
     _mul_mat_typed("mul_mat_q5_1", w_dev, K, M, x_dev, N, y_dev, algo, ldy, stream, w_off, x_off, y_off)
 
 
+def mul_mat_f16(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_off=0, x_off=0, y_off=0):
+    """F16 rows (2 * K bytes each, 16-byte aligned, K % 32 == 0) x f32 [N][K] -> f32 y[n * ldy + m]; algo 0 auto (exact
+    mode, or K too long for the GEMV: 4; N from the GEMM threshold: 9; else 1), 1 GEMV (column tiles), 4 exact and 9
+    f16-MFMA GEMM (the attention's F16 x F32 kernels; ldy == M only)."""
+    _mul_mat_typed("mul_mat_f16", w_dev, K, M, x_dev, N, y_dev, algo, ldy, stream, w_off, x_off, y_off)
+
+
 def dequantize_q5_K(wq_dev, K, M, w_dev, stream=None):
     check(load().ggml_hip_dequantize_q5_K(_ptr(wq_dev), K, M, _ptr(w_dev), stream), "dequantize_q5_K")
 
@@ -524,6 +534,7 @@ class Graph:
 # ggml_tensor mirror (ggml.h:378-414) for driving the tensor ABI from tests
 
 GGML_TYPE_F32, GGML_TYPE_Q4_0 = 0, 2
+GGML_TYPE_F16 = 1
 GGML_TYPE_Q6_K = 14
 GGML_TYPE_Q8_0 = 8
 GGML_TYPE_Q4_1, GGML_TYPE_Q5_0, GGML_TYPE_Q5_1 = 3, 6, 7
@@ -581,6 +592,9 @@ def make_tensor(gtype, ne, data=None, backend=GGML_BACKEND_CPU):
     elif gtype in (GGML_TYPE_Q3_K, GGML_TYPE_Q2_K):
         t.nb[0] = 110 if gtype == GGML_TYPE_Q3_K else 84
         t.nb[1] = t.nb[0] * ne[0] // 256
+    elif gtype == GGML_TYPE_F16:
+        t.nb[0] = 2
+        t.nb[1] = 2 * ne[0]
     else:
         t.nb[0] = 4
         t.nb[1] = 4 * ne[0]
