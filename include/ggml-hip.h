@@ -21,8 +21,9 @@
  * src0 = GGML_TYPE_Q4_K (a "mostly Q4_K" file) is taken on this hook path only
  * with GGML_HIP_Q4_K=1 / ggml_hip_debug_set_q4_K(1) (off by default);
  * the tensor-free ggml_hip_mul_mat_q4_K always runs.  Everything
- * else (Q4_K with its switch off included) returns "cannot" so ggml's
- * CPU path runs, exactly as ggml_cuda_can_mul_mat / ggml_cuda_compute_forward
+ * else (Q4_K with its switch off and every operand on the host included;
+ * between device operands it is served from the host copy, since ggml's CPU
+ * op cannot run there) returns "cannot" so ggml's CPU path runs, exactly as ggml_cuda_can_mul_mat / ggml_cuda_compute_forward
  * return false for what they do not handle.
  *
  * Numerics (pinned by tests/): the q8_0 activation bytes are bit-exact to the
@@ -274,7 +275,9 @@ int ggml_hip_debug_q45k_auto_algo(int type, int64_t K, int64_t M, int64_t N);
  * the previous value. */
 int ggml_hip_debug_set_q45k_gemm_min_n(int n);
 /* the hook path (can_mul_mat, transform_tensor, compute_forward, ggml_hip_mul_mat) takes GGML_TYPE_Q4_K tensors
- * only while this switch is on; off by default (or GGML_HIP_Q4_K=1 in the environment).  Returns the previous
+ * only while this switch is on; off by default (or GGML_HIP_Q4_K=1 in the environment).  Off, a Q4_K matrix stays a
+ * CPU tensor on a host copy; a mul_mat of it whose src1 or dst is a device tensor (an offloaded layer) is still
+ * computed here, from that copy, because ggml's CPU op asserts host operands.  Returns the previous
  * value (0 / 1).  Tensors uploaded while it was on stay on the device, keep being served by
  * compute_forward after it is turned off (their data is not on the host), and are freed by ggml_hip_free_data. */
 int ggml_hip_debug_set_q4_K(int on);

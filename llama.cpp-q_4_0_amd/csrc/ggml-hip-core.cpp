@@ -814,7 +814,11 @@ int q4k_set_enabled(int on) {
 // The hook path's two questions about a weight type.  With the Q4_K switch off every entry point treats a
 // host-resident Q4_K tensor as a type no device op reads; a Q4_K weight that transform_tensor uploaded while the
 // switch was on keeps being served after it is turned off: its data is on the device, so ggml's CPU op could not
-// read it.
+// read it.  The switch decides for all-host nodes only: in an offloaded layer of a Q4_K file the matrix stays on
+// transform_tensor's host copy while src1 and dst are device tensors (llama.cpp's offload_func), and ggml.c's CPU
+// mul_mat asserts host operands (ggml.c:15650), so such a node is served like any host weight of a served type
+// (mul_mat_node's residency cache / upload branch), as the reference's backend never declines once an operand is on
+// the device.
 bool f16_weight(const tensor *t) {
     return t && t->type == gabi::TYPE_F16 && t->op == gabi::OP_NONE && t->ne[2] == 1 && t->ne[3] == 1 && t->ne[0] > 0 &&
            t->ne[0] % ROW_F16.k_granule == 0 && is_contiguous(t);
@@ -828,7 +832,9 @@ int hook_weight_type(const tensor *src0, const tensor *src1, const tensor *dst) 
     // an F16 src0 is a weight only as a 2-D leaf: the K and V views of the attention (permuted, transposed, 3-D, never
     // leaves) keep the F16 x F32 device op and its fusions
     if (src0->type == gabi::TYPE_F16 && !f16_weight(src0)) return gabi::TYPE_COUNT;
-    if (src0->type == gabi::TYPE_Q4_K && !q4k_enabled() && !(on_device(src0) && src0->extra)) return gabi::TYPE_COUNT;
+    if (src0->type == gabi::TYPE_Q4_K && !q4k_enabled() && !(on_device(src0) && src0->extra) && !on_device(src1) &&
+        !on_device(dst))
+        return gabi::TYPE_COUNT;
     return src0->type;
 }
 

@@ -193,7 +193,8 @@ const WeightType *weight_type(int type);                // null: the type has no
 int auto_algo(const WeightType &t, int64_t K, int64_t N);   // what algo 0 runs now (no device needed)
 int check_operands(const WeightType &t, const void *w, int64_t K, int64_t M, const float *x, int64_t N, const float *y,
                    int64_t ldy);
-// the hook path takes Q4_K tensors only with this switch on (GGML_HIP_Q4_K=1 / ggml_hip_debug_set_q4_K; default off)
+// the hook path takes Q4_K tensors only with this switch on (GGML_HIP_Q4_K=1 / ggml_hip_debug_set_q4_K; default off);
+// off, a host Q4_K weight between device operands is still served (hook_weight_type)
 bool q4k_enabled();
 int q4k_set_enabled(int on);                            // returns the previous value (0 / 1)
 // the hook path (ggml-hip-tensor.cpp): is `type` a device weight type now / the weight type whose mul_mat this

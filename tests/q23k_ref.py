@@ -71,16 +71,17 @@ def _split(wq, K, q3):
     return split_q2_K(wq, K)
 
 
-def random_q23_K(rng, M, K, q3, special=True):
+def random_q23_K(rng, M, K, q3, special=True, d_scale=1.0):
     """Fresh valid rows: random scale / hmask / qs bytes and finite fp16 d (dmin) (any such bytes form a valid block),
     with zero, negative and fp16-subnormal d / dmin mixed in, and blocks whose scales are all -32 and all 31 (Q3_K),
-    whose scales and mins are all 0 and all 15 (Q2_K), and, Q3_K, whose hmask is all set and all clear."""
+    whose scales and mins are all 0 and all 15 (Q2_K), and, Q3_K, whose hmask is all set and all clear.
+    d_scale multiplies the spread of d and dmin (1.0: the bytes every caller without it has always got)."""
     nb = K // QK_K
     bs = block_bytes(q3)
     b = rng.integers(0, 256, size=(M, nb, bs), dtype=np.uint8)
     n = M * nb
     for off, scale in ((108, 0.01),) if q3 else ((80, 0.01), (82, 0.005)):
-        d = (rng.standard_normal(n) * scale).astype(np.float16)        # both signs
+        d = (rng.standard_normal(n) * (scale * d_scale)).astype(np.float16)        # both signs
         if special:
             d[rng.integers(0, n, size=max(1, n // 16))] = np.float16(0.0)
             idx = rng.integers(0, n, size=max(1, n // 16))

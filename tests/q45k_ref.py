@@ -51,15 +51,16 @@ def split_q45_K(wq, K, qh):
     return d, dmin, sc, m, q.reshape(M, nb, 8, 32)
 
 
-def random_q45_K(rng, M, K, qh, special=True):
+def random_q45_K(rng, M, K, qh, special=True, d_scale=1.0):
     """Fresh valid rows: random scales / qh / qs bytes and finite fp16 d, dmin (any such bytes form a valid block),
-    with zero, negative and fp16-subnormal d / dmin and blocks of all-0 and all-63 scales and mins mixed in."""
+    with zero, negative and fp16-subnormal d / dmin and blocks of all-0 and all-63 scales and mins mixed in.
+    d_scale multiplies the spread of d and dmin (1.0: the bytes every caller without it has always got)."""
     nb = K // QK_K
     bs = block_bytes(qh)
     b = rng.integers(0, 256, size=(M, nb, bs), dtype=np.uint8)
     n = M * nb
     for off, scale in ((0, 0.01), (2, 0.005)):
-        d = (rng.standard_normal(n) * scale).astype(np.float16)        # both signs
+        d = (rng.standard_normal(n) * (scale * d_scale)).astype(np.float16)        # both signs
         if special:
             d[rng.integers(0, n, size=max(1, n // 16))] = np.float16(0.0)
             idx = rng.integers(0, n, size=max(1, n // 16))

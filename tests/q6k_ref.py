@@ -40,12 +40,13 @@ def split_q6_K(wq, K):
     return d, sc, q.reshape(M, nb, QK_K)
 
 
-def random_q6_K(rng, M, K, special_d=True):
+def random_q6_K(rng, M, K, special_d=True, d_scale=1.0):
     """Fresh valid block_q6_K rows: random ql / qh / scales bytes and finite fp16 d (any such bytes form a valid
-    block), with zero, negative and fp16-subnormal d mixed in."""
+    block), with zero, negative and fp16-subnormal d mixed in.  d_scale multiplies the spread of d (1.0: the bytes
+    every caller without it has always got)."""
     nb = K // QK_K
     b = rng.integers(0, 256, size=(M, nb, Q6KB), dtype=np.uint8)
-    d = (rng.standard_normal((M, nb)) * 0.01).astype(np.float16)
+    d = (rng.standard_normal((M, nb)) * (0.01 * d_scale)).astype(np.float16)
     if special_d:
         flat = d.reshape(-1)
         n = flat.size
