@@ -313,20 +313,44 @@ int ggml_hip_debug_set_q23k_gemm_min_n(int n);
 /* F16 WEIGHTS (contiguous rows of K halves; dev_w 16-byte aligned, K % 32 == 0: the matrices of a "mostly F16" file)
  * x F32 -> F32 with the semantics of ggml_compute_forward_mul_mat_f16_f32 (ggml.c:11026): x is rounded to fp16
  * (round to nearest even) and every product of two fp16 values is exact in fp32.  y[n * ldy + m], ldy >= M.
- * Stream-ordered and capturable; no workspace.  No byte outside [dev_w, dev_w + M * K * 2) is read.  Status codes as
- * for the q4_0 entry points; N == 0 is a no-op.  algo: 0 auto (4 in exact mode and for a K the GEMV cannot take; else
+ * Stream-ordered and capturable; no workspace but algo 11's.  No byte outside [dev_w, dev_w + M * K * 2) is read.  Status
+ * codes as for the q4_0 entry points; N == 0 is a no-op.  algo: 0 auto (4 in exact mode; else 11 when N >= the
+ * weight-shaped GEMM's threshold, default never, at any K; else 4 for a K the GEMV cannot take; else
  * 9 when N >= the GEMM threshold; else 1), 1 GEMV (K <= 65536) with the fp16 rounding of x fused in and one fixed
  * order of the fp32 additions per K (csrc/f16_w.hip, restated in tests/f16w_ref.py; column tiles of at most 8 above
  * that, bitwise the per-tile calls; y does not depend on N, M or the launch geometry) — within the fp32-accumulation
  * bound of the reference, 4 exact: bit-identical to ggml_vec_dot_f16 in its AVX2 / F16C schedule (the kernels of
  * the attention's F16 x F32 products, ldy == M only), 9 prefill GEMM on the f16 matrix cores (the attention's
- * fast-mode kernel, ldy == M only; within the same bound).  Anything else (2, 3, 5, 6, 7 and 8 included) ->
- * GGML_HIP_ERR_INVALID, before anything else is checked; 4 or 9 with ldy != M -> GGML_HIP_ERR_UNSUPPORTED. */
+ * fast-mode kernel, ldy == M only; within the same bound), 11 prefill GEMM decomposed for weight shapes
+ * (csrc/f16_w_gemm.hip: v_mfma_f32_32x32x16_f16 on 64-element K chunks, narrow row tiles and a K split where the
+ * shape alone does not fill the device).  Algo 11 takes any K % 32 == 0, any M, N >= 1 and any ldy >= M, reads no
+ * byte outside dev_w's M * K * 2 and dev_x's N * K * 4 and writes only the M columns of the N rows of y.  Per output
+ * |y - S| <= 1e-5 * sum |W * fp16(x)| of the float64 sum S of the exact products (algo 9's bound); it is
+ * deterministic, and not bitwise algo 1 or 9: the switch moves a result within the bound, and exact mode never takes
+ * it.  The order of one output's additions depends on K and on the plan (one of three tile / K-split
+ * decompositions, a pure function of K, M, N and the device's CU count) and on nothing else, so with the plan pinned
+ * (ggml_hip_debug_set_f16w_wgemm_plan) a column or row slice of a call is bitwise the call on that slice.  It uses
+ * the stream's workspace: the fp16 image of x (2 * N * K bytes) and, for a plan that splits K, one fp32 [N][M] slab
+ * per slice (at most 4), added in slice order by a second launch (no atomics, no waiting between workgroups);
+ * ggml_hip_reserve_workspace_mm(K, N, M) reserves it for the plan in force at the time of the reservation, and a
+ * reserved call is capturable.  Anything else (2, 3, 5, 6, 7, 8 and 10 included) -> GGML_HIP_ERR_INVALID, before
+ * anything else is checked; 4 or 9 with ldy != M, and 11 on a shape whose tiles exceed one grid ->
+ * GGML_HIP_ERR_UNSUPPORTED (auto then falls back to the rule without 11). */
 int ggml_hip_mul_mat_f16(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N,
                          float *dev_y, int64_t ldy, int algo, void *stream);
-/* debug, no device needed: the algo that algo 0 of ggml_hip_mul_mat_f16 would run now: 1, 4 or 9; a bad K ->
+/* debug, no device needed: the algo that algo 0 of ggml_hip_mul_mat_f16 would run now: 1, 4, 9 or 11; a bad K ->
  * GGML_HIP_ERR_INVALID */
 int ggml_hip_debug_f16w_auto_algo(int64_t K, int64_t M, int64_t N);
+/* debug: the smallest N at which auto takes the weight-shaped F16 GEMM (algo 11).  Default never
+ * (GGML_HIP_F16W_WGEMM_MIN_N; the measured rows are in DESIGN.md section 4b); values below 9 count as 9; -1 restores
+ * the environment value or the default.  Returns the previous value. */
+int ggml_hip_debug_set_f16w_wgemm_min_n(int n);
+/* debug: pin algo 11's plan: 0 auto, 1 (32 rows x 64 columns, K split over the waves and 4 workgroups), 2 (64 x 128,
+ * K split 2), 3 (128 x 128, no split).  Returns the previous value; anything else -> GGML_HIP_ERR_INVALID. */
+int ggml_hip_debug_set_f16w_wgemm_plan(int plan);
+/* debug, no device needed: the plan auto would take now for this shape (the current device's CU count; 256 where no
+ * device is initialised), whatever is pinned */
+int ggml_hip_debug_f16w_wgemm_plan(int64_t K, int64_t M, int64_t N);
 /* debug: the smallest N at which auto takes the F16 GEMM (algo 9).  Default 32 (GGML_HIP_F16W_GEMM_MIN_N; the
  * measured rows are in DESIGN.md section 4b); values below 9 count as 9; -1 restores the environment value or the
  * default.  Returns the previous value. */

@@ -226,9 +226,25 @@ int ggml_hip_mul_mat_f16(const void *dev_w, int64_t K, int64_t M, const float *d
     return mul_mat_type(gabi::TYPE_F16, dev_w, K, M, dev_x, N, dev_y, ldy, algo, stream);
 }
 
-int ggml_hip_debug_f16w_auto_algo(int64_t K, int64_t M, int64_t N) { return debug_auto_algo(gabi::TYPE_F16, K, M, N); }
+int ggml_hip_debug_f16w_auto_algo(int64_t K, int64_t M, int64_t N) {
+    if (K <= 0 || K % 32 || M <= 0 || N < 0) return fail(GGML_HIP_ERR_INVALID, "bad shape");
+    return auto_algo_f16w(K, M, N);
+}
 
 int ggml_hip_debug_set_f16w_gemm_min_n(int n) { return weight_type(gabi::TYPE_F16)->min_n->set(n); }
+
+int ggml_hip_debug_set_f16w_wgemm_min_n(int n) { return f16w_wgemm_min_n()->set(n); }
+
+int ggml_hip_debug_set_f16w_wgemm_plan(int plan) {
+    if (plan < 0 || plan > ghip::F16W_WGEMM_PLANS) return fail(GGML_HIP_ERR_INVALID, "plan must be 0 (auto) ... 3");
+    return ghip::gemm_f16w_set_plan(plan);
+}
+
+// the plan auto would take now on the current device (256 CUs where there is none); no device is initialised for it
+int ggml_hip_debug_f16w_wgemm_plan(int64_t K, int64_t M, int64_t N) {
+    if (K <= 0 || K % 32 || M <= 0 || N < 0) return fail(GGML_HIP_ERR_INVALID, "bad shape");
+    return ghip::gemm_f16w_auto_plan(K, M, N, g_device_count > 0 ? g_dev[current_device()].info.num_cus : 0);
+}
 
 /* not in the public header: force the Q8_0 GEMV's launch policy (tests: every policy gives the same y bitwise) */
 int ggml_hip_debug_set_q8_0_gemv_policy(int map, int depth, int wg_per_cu) {
@@ -364,7 +380,9 @@ int ggml_hip_reserve_workspace_mm(int64_t K, int64_t N, int64_t M) {
     ensure_init();
     if (g_device_count == 0) return fail(GGML_HIP_ERR_DEVICE, "no HIP device");
     if (K <= 0 || N < 0 || M < 0) return fail(GGML_HIP_ERR_INVALID, "bad shape");
-    return reserve_workspace(current_device(), std::max(workspace_bytes_mm(K, N, M), workspace_bytes_q81(K, N)));
+    const int id = current_device();
+    return reserve_workspace(id, std::max({workspace_bytes_mm(K, N, M), workspace_bytes_q81(K, N),
+                                           workspace_bytes_f16w_gemm(id, K, N, M)}));
 }
 
 // ------------------------------------------------------------------------------------------

@@ -355,6 +355,11 @@ static GemmMinN g_q23k_min_n{"GGML_HIP_Q23K_GEMM_MIN_N", INT_MAX};
 // from 32 on all three shapes, so the default stays 32.  The MFMA kernel, built for K = 128, is flat in N at ~93 / 97 /
 // 250 us up to N = 512 (0.36 / 0.93 / 0.36 TB/s of weight bytes): a weight-shaped F16 GEMM is DESIGN §8's.
 static GemmMinN g_f16w_min_n{"GGML_HIP_F16W_GEMM_MIN_N", 32};
+// F16 (algo 11 = k_gemm_f16w, f16_w_gemm.hip, the GEMM decomposed for weight shapes): "never" by default, so auto runs
+// the rule above at every N until the user sets the threshold (the measured table is in DESIGN §4b; tools/f16w_bench.py,
+// profiles/f16w_wgemm.json).  Its y is within the bound of the GEMV's and of algo 9's, not bitwise either.
+static GemmMinN g_f16w_wgemm_min_n{"GGML_HIP_F16W_WGEMM_MIN_N", INT_MAX};
+GemmMinN *f16w_wgemm_min_n() { return &g_f16w_wgemm_min_n; }
 
 // the K a type's GEMV takes: one token's q8_K image in the LDS for the k-quants (w2 of a 30B / 65B model has K =
 // 17920 / 22016), one token's q8_0 for Q8_0
@@ -444,9 +449,10 @@ static const WeightType ROW_Q5_1 = {
     64, 4, ERR_DQ_Q5X};
 
 // F16 (f16_w.hip; the "mostly F16" files): contiguous rows of K halves, 16-byte aligned, K % 32 == 0 (the reference's
-// GGML_CUDA_DMMV_X).  There is nothing to dequantize and no kernel of its own beside the GEMV: exact mode (algo 4) and
-// the GEMM (algo 9) are the attention's F16 x F32 kernels (ggml_ops.hip) on contiguous strides, unchanged.  The exact
-// kernels where the GEMV cannot take K.
+// GGML_CUDA_DMMV_X).  There is nothing to dequantize: exact mode (algo 4) and the table's GEMM (algo 9) are the
+// attention's F16 x F32 kernels (ggml_ops.hip) on contiguous strides, unchanged.  The exact kernels where the GEMV
+// cannot take K.  The weight-shaped GEMM (algo 11) sits in front of this row's rule behind a threshold of its own
+// (auto_algo_f16w).
 static const WeightType ROW_F16 = {
     32, 16, (int64_t)1 << 31,
     9, 4, &g_f16w_min_n, gemv_takes_k_f16w, mul_mat_f16w_dev,
@@ -473,6 +479,20 @@ int auto_algo(const WeightType &t, int64_t K, int64_t N) {
     if (exact_mode()) return 4;
     if (!t.gemv_takes_k(K)) return t.no_gemv_algo;
     return N >= t.min_n->get() ? t.gemm_algo : 1;
+}
+
+// F16: exact mode -> 4; from the weight-shaped GEMM's threshold (default "never") and where its launch takes the shape
+// -> 11, at any K (it has no LDS-bound K limit); else the table's rule
+int auto_algo_f16w(int64_t K, int64_t M, int64_t N) {
+    if (exact_mode()) return 4;
+    if (N >= g_f16w_wgemm_min_n.get() && ghip::gemm_f16w_supported(K, M, N)) return 11;
+    return auto_algo(ROW_F16, K, N);
+}
+
+// the workspace of algo 11 (the fp16 image of x + the K-slice slabs of the plan the call would run now on device id;
+// 256 CUs where there is no device)
+size_t workspace_bytes_f16w_gemm(int id, int64_t K, int64_t N, int64_t M) {
+    return ghip::gemm_f16w_ws_bytes(K, M, N, id >= 0 && id < g_device_count ? g_dev[id].info.num_cus : 0);
 }
 
 // OK with N == 0 means there is nothing to run: the steps behind it are not checked then
@@ -694,19 +714,31 @@ static int mul_mat_q2k_dev(const void *w, int64_t K, int64_t M, const float *x, 
 
 // F16 (f16_w.hip, ggml_ops.hip): algo 1 = k_gemv_f16w in column tiles; algo 4 = op_mul_mat_f16_f32's bitwise kernels
 // (ggml_vec_dot_f16 in its AVX2 / F16C schedule) and algo 9 = its MFMA kernel, both on contiguous strides.  Those
-// launchers write y as [N][M] with no row pitch, so 4 and 9 take ldy == M only (the hook never passes another).  An
+// launchers write y as [N][M] with no row pitch, so 4 and 9 take ldy == M only (the hook never passes another).
+// Algo 11 = k_gemm_f16w (f16_w_gemm.hip) on the fp16 image of x in the workspace: any ldy >= M, any K % 32 == 0.  An
 // algo the type rejects is refused before anything else, an empty call included.
 static int mul_mat_f16w_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
                             hipStream_t s) {
-    if (algo != 0 && algo != 1 && algo != 4 && algo != 9) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1, 4 or 9");
+    if (algo != 0 && algo != 1 && algo != 4 && algo != 9 && algo != 11)
+        return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1, 4, 9 or 11");
     const WeightType &t = ROW_F16;
     const int rc = check_operands(t, w, K, M, x, N, y, ldy);
     if (rc != GGML_HIP_OK || N == 0) return rc;
     const int id = current_device();
-    if (algo == 0) algo = auto_algo(t, K, N);
+    if (algo == 0) algo = auto_algo_f16w(K, M, N);
     if (algo == 1) {
         if (!t.gemv_takes_k(K)) return fail(GGML_HIP_ERR_UNSUPPORTED, t.err_gemv_k);
         HIP_RET(ghip::gemv_f16w(w, K, M, x, N, y, ldy, g_dev[id].info, s));
+        return GGML_HIP_OK;
+    }
+    if (algo == 11) {
+        if (!ghip::gemm_f16w_supported(K, M, N))
+            return fail(GGML_HIP_ERR_UNSUPPORTED, "too many tiles for one grid of the F16 GEMM (algo 11); split rows or columns");
+        void *ws = nullptr;
+        const size_t need = workspace_bytes_f16w_gemm(id, K, N, M);
+        const int wrc = stream_workspace(id, s, need, &ws);
+        if (wrc != GGML_HIP_OK) return wrc;
+        HIP_RET(ghip::gemm_f16w(w, K, M, x, N, y, ldy, ws, need, g_dev[id].info, s));
         return GGML_HIP_OK;
     }
     if (ldy != M) return fail(GGML_HIP_ERR_UNSUPPORTED, "the exact and MFMA F16 kernels (algo 4, 9) need ldy == M");

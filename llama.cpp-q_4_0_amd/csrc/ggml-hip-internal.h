@@ -191,6 +191,10 @@ struct WeightType {
 };
 const WeightType *weight_type(int type);                // null: the type has no row
 int auto_algo(const WeightType &t, int64_t K, int64_t N);   // what algo 0 runs now (no device needed)
+// F16 only: the rule with the weight-shaped GEMM (algo 11) in front of the table's, its threshold, its workspace
+int auto_algo_f16w(int64_t K, int64_t M, int64_t N);
+GemmMinN *f16w_wgemm_min_n();
+size_t workspace_bytes_f16w_gemm(int id, int64_t K, int64_t N, int64_t M);
 int check_operands(const WeightType &t, const void *w, int64_t K, int64_t M, const float *x, int64_t N, const float *y,
                    int64_t ldy);
 // the hook path takes Q4_K tensors only with this switch on (GGML_HIP_Q4_K=1 / ggml_hip_debug_set_q4_K; default off);

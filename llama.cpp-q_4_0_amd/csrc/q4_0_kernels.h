@@ -247,6 +247,19 @@ hipError_t gemm_q5x1(bool qh, const void *W, int64_t K, int64_t M, const int8_t 
 int gemv_f16w_max_tokens(int64_t K);
 hipError_t gemv_f16w(const void *W, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
                      const DeviceInfo &dev, hipStream_t s);
+// prefill (f16_w_gemm.hip): the f16-MFMA GEMM decomposed for weight shapes, any K % 32 == 0 (N K < 2^31), M, N >= 1,
+// ldy >= M; y within the fp32-accumulation bound, its order a function of K and the plan alone.  A plan (1 ..
+// F16W_WGEMM_PLANS) is a pure function of (K, M, N, CU count; 256 CUs where num_cus <= 0) unless one is pinned
+// (set_plan: 0 auto, returns the previous).  ws: ws_bytes(K, M, N, num_cus) bytes for the fp16 image of x and the
+// plan's K-slice slabs.  supported: the index products and every plan's grid fit one launch.
+constexpr int F16W_WGEMM_PLANS = 3;
+int gemm_f16w_plan(int64_t K, int64_t M, int64_t N, int num_cus);        // the pinned plan, or auto's
+int gemm_f16w_auto_plan(int64_t K, int64_t M, int64_t N, int num_cus);
+int gemm_f16w_set_plan(int plan);
+bool gemm_f16w_supported(int64_t K, int64_t M, int64_t N);
+size_t gemm_f16w_ws_bytes(int64_t K, int64_t M, int64_t N, int num_cus);
+hipError_t gemm_f16w(const void *W, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, void *ws,
+                     size_t ws_bytes, const DeviceInfo &dev, hipStream_t s);
 
 // Multi-GPU helper: y[n*ldy + row0[r] + i] = slab[r][n][i] for i < rows[r] (gather compaction).
 // row_begin travels as a kernel argument (no host->device copy, capture-safe)

@@ -19,7 +19,15 @@ smallest swept N from which the MFMA arm beats the GEMV arm at every larger swep
 f16w_gemm_min_n); null if it never does.  The arms are checked against each other within 1e-3 of the largest |y|
 before they are timed.  Fails without a HIP device.
 
-    python tools/f16w_bench.py [--what decode|prefill|both] [--rounds 10] [--out-dir profiles]
+Weight-shaped GEMM (profiles/f16w_wgemm.json; --what wgemm).  The three layer shapes and the lm_head, N = 9 .. 512, over
+the same rotation, graphs and alternation: algo 1 (GEMV column tiles), algo 9 (k_mul_mat_f16_f32_mfma) and algo 11
+(k_gemm_f16w, csrc/f16_w_gemm.hip) with the plan auto takes, and algo 11 under each pinned plan (the per-plan sweep the
+plan rule is held against).  Per cell and arm: median, min and max over rounds; for algo 11 the fraction of the
+derived floor max(weight bytes / 8 TB/s, 2 K M N / 2.5 PF).  algo 11 WINS a cell where its median is below both other
+arms' and its max below their min (the spreads do not overlap).  `recommended_min_n` is the smallest swept N from which
+it wins every cell of every layer shape; null if there is none.
+
+    python tools/f16w_bench.py [--what decode|prefill|wgemm|both] [--rounds 10] [--out-dir profiles]
 """
 import argparse
 import json
@@ -37,6 +45,8 @@ DECODE_SHAPES = LAYER_SHAPES + ((4096, 32000),)
 DECODE_NS = (1, 4, 8)
 SWEEP_NS = (9, 16, 32, 64, 128, 512)
 HBM_TBS = 8.0
+MFMA_PFS = 2.5
+WGEMM_PLANS = (1, 2, 3)
 DB = ggml_hip.DeviceBuffer
 ARMS = {"gemv": 1, "bitwise": 4, "mfma": 9}
 
@@ -171,9 +181,80 @@ def prefill(L, s, a):
                       "events, arms interleaved, median over rounds"}
 
 
+def wgemm(L, s, a):
+    rng = np.random.default_rng(0xF16F)
+    pin = L.ggml_hip_debug_set_f16w_wgemm_plan
+    # arm -> (algo, pinned plan; 0 auto)
+    arms = {"gemv": (1, 0), "mfma": (9, 0), "wgemm": (11, 0)}
+    arms.update({f"wgemm_p{p}": (11, p) for p in WGEMM_PLANS})
+    shapes = []
+    for K, M in DECODE_SHAPES:
+        wd, mat, copies = rotation(rng, K, M, a.set_mb)
+        nmax = max(SWEEP_NS)
+        xd = DB.from_array(rng.standard_normal((nmax, K)).astype(np.float32))
+        yd = {name: DB(nmax * M * 4) for name in arms}
+        for p in WGEMM_PLANS:                                  # the workspace of every plan, ahead of the captures
+            pin(p)
+            ggml_hip.check(L.ggml_hip_reserve_workspace_mm(K, nmax, M), "reserve")
+        pin(0)
+        sweep = []
+        for N in SWEEP_NS:
+            def call(name, i):
+                algo, plan = arms[name]
+                pin(plan)
+                ggml_hip.mul_mat_f16(wd, K, M, xd, N, yd[name], algo=algo, stream=s, w_off=i * mat)
+                pin(0)
+            ys = {}
+            for name in arms:
+                call(name, 0)
+                ggml_hip.check(L.ggml_hip_stream_synchronize(s))
+                ys[name] = yd[name].download((N, M), np.float32)
+                if not np.abs(ys[name] - ys["gemv"]).max() <= 1e-3 * np.abs(ys["gemv"]).max():
+                    sys.exit(f"f16w_bench wgemm: arm {name} differs from gemv at K = {K}, M = {M}, N = {N}")
+            graphs, per_graph = {}, {}
+            for name in arms:
+                g = ggml_hip.Graph(s)
+                with g:
+                    for i in range(copies):
+                        call(name, i)
+                graphs[name], per_graph[name] = g, copies
+            us = timed_rounds(L, s, graphs, a.rounds, a.settle_ms, per_graph, "f16w_bench wgemm")
+            floor = max(mat / (HBM_TBS * 1e12), 2.0 * K * M * N / (MFMA_PFS * 1e15)) * 1e6
+            row = {"N": N, "floor_us": round(floor, 2), "auto_plan": L.ggml_hip_debug_f16w_wgemm_plan(K, M, N)}
+            for name in arms:
+                row.update({f"{name}_{k}": v for k, v in stats(us[name]).items()})
+            row["wgemm_floor_frac"] = round(floor / row["wgemm_us"], 3)
+            row["wgemm_wins"] = all(row["wgemm_us"] < row[f"{o}_us"] and row["wgemm_us_max"] < row[f"{o}_us_min"]
+                                    for o in ("gemv", "mfma"))
+            best = min(WGEMM_PLANS, key=lambda p: row[f"wgemm_p{p}_us"])
+            row["best_plan"] = best
+            row["auto_plan_over_best"] = round(row[f"wgemm_p{row['auto_plan']}_us"] / row[f"wgemm_p{best}_us"], 3)
+            sweep.append(row)
+            del graphs
+        shapes.append({"K": K, "M": M, "weight_bytes": mat, "copies": copies, "sweep": sweep})
+        for b in [wd, xd] + list(yd.values()):
+            b.free()
+    rec = None
+    layer = [sh for sh in shapes if (sh["K"], sh["M"]) in LAYER_SHAPES]
+    for i in reversed(range(len(SWEEP_NS))):
+        if not all(sh["sweep"][i]["wgemm_wins"] for sh in layer):
+            break
+        rec = SWEEP_NS[i]
+    wins = {n: all(sh["sweep"][SWEEP_NS.index(n)]["wgemm_wins"] for sh in layer) for n in (64, 512)}
+    return {"bench": "f16w_wgemm", "set_mb": a.set_mb, "rounds": a.rounds, "settle_ms": a.settle_ms, "hbm_TBs": HBM_TBS,
+            "mfma_PFs": MFMA_PFS, "shapes": shapes, "recommended_min_n": rec,
+            "wins_on_every_layer_shape_at_64_and_512": wins,
+            "arms": {"gemv": "algo 1, column tiles of gemv_f16w_max_tokens(K)", "mfma": "algo 9, k_mul_mat_f16_f32_mfma",
+                     "wgemm": "algo 11, k_gemm_f16w, the plan auto takes (auto_plan)",
+                     "wgemm_pK": "algo 11 with plan K pinned: 1 = 32 x 64 tiles, K split over the waves and 4 workgroups; "
+                                 "2 = 64 x 128, K split 2; 3 = 128 x 128, no split"},
+            "timing": "HIP-graph replays over a rotation of weight copies larger than the last-level cache, device "
+                      "events, arms interleaved, median / min / max over rounds; algo 11's x image and slab sum included"}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", choices=("decode", "prefill", "both"), default="both")
+    ap.add_argument("--what", choices=("decode", "prefill", "wgemm", "both"), default="both")
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--settle-ms", type=float, default=40.0)
     ap.add_argument("--set-mb", type=int, default=512)
@@ -185,8 +266,9 @@ def main():
     ggml_hip.check(L.ggml_hip_set_device(0))
     ggml_hip.check(L.ggml_hip_set_exact(0))
     s = L.ggml_hip_default_stream()
-    for what, fn, out in (("decode", decode, "f16w_gemv.json"), ("prefill", prefill, "f16w_gemm.json")):
-        if a.what not in (what, "both"):
+    for what, fn, out in (("decode", decode, "f16w_gemv.json"), ("prefill", prefill, "f16w_gemm.json"),
+                          ("wgemm", wgemm, "f16w_wgemm.json")):
+        if a.what != what and (a.what != "both" or what == "wgemm"):
             continue
         line = json.dumps(fn(L, s, a))
         print(line, flush=True)
