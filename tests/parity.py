@@ -90,3 +90,46 @@ def check_y(y_got, y_ref, s_abs, rtol=1e-3, atol_blocks=1e-6):
     rel = (err[big] / np.abs(y_ref[big])).max() if big.any() else 0.0
     REPORT.append((os.environ.get("PYTEST_CURRENT_TEST", "?").split(" ")[0], int(err.size), float(rel), need_max))
     return float(rel), float(err.max())
+
+
+def check_y_terms(y_got, y64, s_abs, nb, roundings=2):
+    """Assert |y - y64| <= 1.01 * (nb + roundings) * 2^-24 * S_abs, the bound with no relative term; return the
+    multiple of 2^-24 * S_abs the worst element needed (a record of what was measured, not a threshold).
+
+    y64, S_abs: block_terms on the oracle's q8_0 bytes of x (the exact sum of the exact block terms).  Derivation: the
+    integer block sums are exact and d_w * d_x is exact in fp32 (two 11-bit significands), so term b reaches the
+    accumulator as fl(p * sumi) or inside an fma: at most `roundings` roundings before the accumulation (2 covers
+    (d_x * sumi) * d_w), each of relative size 2^-24 of |term|.  Whatever the tree, a term then passes through at most
+    nb - 1 additions, each rounding a partial sum that is at most S_abs in magnitude (to first order): in all
+    (nb - 1 + roundings) * 2^-24 * S_abs, rounded up to nb + roundings; the factor 1.01 covers the second-order terms
+    ((1 + 2^-24)^nb - 1 - nb 2^-24 < 1e-3 nb 2^-24 for nb <= 2^13) and the final rounding of the comparison itself.
+    A caller whose kernel rounds more often, or keeps the nibble dot and the -8 sum(q) correction as separate floats,
+    passes the count (or the larger magnitude sum as s_abs) read from the kernel's code."""
+    y_got = np.asarray(y_got, dtype=np.float64)
+    y64 = np.asarray(y64, dtype=np.float64)
+    s_abs = np.asarray(s_abs, dtype=np.float64)
+    assert y_got.shape == y64.shape == s_abs.shape
+    err = np.abs(y_got - y64)
+    u = 2.0 ** -24
+    with np.errstate(divide="ignore", invalid="ignore"):
+        need = np.where(s_abs > 0, err / (u * s_abs), np.where(err > 0, np.inf, 0.0))
+    need_max = float(need.max()) if need.size else 0.0
+    bad = ~(err <= 1.01 * (nb + roundings) * u * s_abs)           # a NaN in y is out of bound
+    if bad.any():
+        i = tuple(np.argwhere(bad)[0])
+        raise AssertionError(f"{bad.sum()} elements outside (nb + {roundings}) * 2^-24 * S_abs (nb = {nb}); first {i}: "
+                             f"got {y_got[i]!r} exact {y64[i]!r} needs {need[i]:.3g} * 2^-24 * S_abs")
+    return need_max
+
+
+def assert_equal_values(y_got, y64):
+    """y == float32(y64) as values (-0.0 == +0.0 is accepted, nothing else differs): the order-free comparison."""
+    y_got = np.asarray(y_got)
+    assert y_got.dtype == np.float32 and y_got.shape == y64.shape
+    want = np.asarray(y64, dtype=np.float64).astype(np.float32)
+    assert np.array_equal(want.astype(np.float64), y64), "y64 is not representable in fp32: not an order-free case"
+    bad = ~(y_got == want)
+    if bad.any():
+        i = tuple(np.argwhere(bad)[0])
+        raise AssertionError(f"{bad.sum()} of {bad.size} elements differ from float32(y64); first (n, m) = {i}: "
+                             f"got {y_got[i]!r} exact {want[i]!r}")

@@ -13,7 +13,8 @@ import pytest
 import oracle as O
 from golden_io import load
 from hip_env import ggml_hip, gpu_available
-from parity import block_terms, check_y, s_abs_exact
+from parity import assert_equal_values, block_terms, check_y, check_y_terms, s_abs_exact
+from q4_0_exact_cases import EXTREME_SHAPE, extreme_order_free
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not gpu_available(), reason="needs a HIP device and libggml_hip.so")]
@@ -736,8 +737,27 @@ def test_gemm9_fp6_extreme_blocks_exact():
         y, _ = gpu_mul_mat(wq, K, x, algo=2)
     finally:
         _gemm_version(-1)
-    _, s_abs = block_terms(wq, xq, K)
+    y64, s_abs = block_terms(wq, xq, K)
     check_y(y, O.mul_mat(wq, K, x, nthreads=4), s_abs, RTOL, ATOL_BLOCKS)
+    # and against the exact block sums with no relative term: k_gemm9 adds one fmaf per block (roundings = 2 covers it)
+    check_y_terms(y, y64, s_abs, K // 32)
+
+
+@pytest.mark.parametrize("wide", [0, 1], ids=["tile128x64", "tile128x128"])
+def test_gemm9_fp6_extreme_blocks_order_free_equal(wide):
+    """The order-free twin of the case above (tests/q4_0_exact_cases.py extreme_order_free): rows of all-0 and all-15
+    nibbles, tokens with every q at +127, at -127, alternating, and 0 but for one element, power-of-two scales: every
+    fp32 summation order is exact, so both k_gemm9 tiles must return float32(y64) itself."""
+    K, M, N = EXTREME_SHAPE
+    c = extreme_order_free(K, M, N)
+    _gemm_version(11)
+    _gemm9_wide(wide)
+    try:
+        y, _ = gpu_mul_mat(c["wq"], K, c["x"], algo=2)
+    finally:
+        _gemm_version(-1)
+        _gemm9_wide(-1)
+    assert_equal_values(y, c["y64"])
 
 
 @pytest.mark.parametrize("v", [8, 10], ids=["int8-image", "fp6-image"])
