@@ -515,11 +515,8 @@ int check_operands(const WeightType &t, const void *w, int64_t K, int64_t M, con
 // which ggml_hip_reserve_workspace reserves.
 static size_t workspace_bytes_q8k(int64_t K, int64_t N) { return (size_t)N * (size_t)(K / QK_K) * Q8KB; }
 static size_t kquant_planes_offset(int64_t K, int64_t N) { return ws_d_offset(K, N); }
-static size_t workspace_bytes_q6k_gemm(int64_t K, int64_t N) {
+static size_t workspace_bytes_kquant_gemm(int64_t K, int64_t N) {          // (without Q5_K / Q4_K's dig)
     return kquant_planes_offset(K, N) + (size_t)N * (size_t)(K / QK_K) * 4;
-}
-static size_t workspace_bytes_q45k_gemm(int64_t K, int64_t N) {
-    return kquant_planes_offset(K, N) + (size_t)N * (size_t)(K / QK_K) * 20;
 }
 
 static bool too_many_tiles(int64_t M, int64_t N) { return ((M + 63) / 64) * ((N + 63) / 64) >= ((int64_t)1 << 31); }
@@ -533,33 +530,72 @@ static int quantize_q8k_ws(int id, const float *x, int64_t K, int64_t N, hipStre
     return GGML_HIP_OK;
 }
 
-// Q6_K (q6_k.hip, q6_k_gemm.hip): algo 5 = the q8_K values of x as planes in the workspace + k_gemm_q6_K
-static int mul_mat_q6k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
-                           hipStream_t s) {
-    const int rc = check_operands(ROW_Q6_K, w, K, M, x, N, y, ldy);
+// The five k-quants (q6_k.hip, q45_k.hip, q23_k.hip; kquant_gemm.h), one body over their rows.  algo 1 = the type's
+// GEMV, 4 = the q8_K blocks of x + the type's exact kernel, the row's gemm_algo (5 Q6_K, 6 Q5_K / Q4_K, 8 Q3_K / Q2_K;
+// each number is valid for its own types only) = the q8_K values of x as planes in the workspace + the type's GEMM on
+// the weights in place, any K % 256 == 0.  Q5_K / Q4_K read the digits of x's sub-block sums from a plane of their
+// own, between qs and d.
+enum class KQuant { Q6_K, Q5_K, Q4_K, Q3_K, Q2_K };
+static int mul_mat_kquant_dev(const WeightType &t, KQuant type, const void *w, int64_t K, int64_t M, const float *x,
+                              int64_t N, float *y, int64_t ldy, int algo, hipStream_t s) {
+    const bool q45 = type == KQuant::Q5_K || type == KQuant::Q4_K, q23 = type == KQuant::Q3_K || type == KQuant::Q2_K;
+    const bool algo_ok = algo == 0 || algo == 1 || algo == 4 || algo == t.gemm_algo;
+    auto bad_algo = [&] { return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1, 4 or " + std::to_string(t.gemm_algo)); };
+    // Q6_K checks the operands first, so its empty call is OK whatever the algo; the others refuse an algo they
+    // reject before anything else, an empty call included
+    if (type != KQuant::Q6_K && !algo_ok) return bad_algo();
+    const int rc = check_operands(t, w, K, M, x, N, y, ldy);
     if (rc != GGML_HIP_OK || N == 0) return rc;
     const int id = current_device();
-    if (algo == 0) algo = auto_algo(ROW_Q6_K, K, N);
+    if (algo == 0) algo = auto_algo(t, K, N);
     if (algo == 1) {
-        if (!ROW_Q6_K.gemv_takes_k(K)) return fail(GGML_HIP_ERR_UNSUPPORTED, ROW_Q6_K.err_gemv_k);
-        HIP_RET(ghip::gemv_q6_K(w, K, M, x, N, y, ldy, g_dev[id].info, s));
+        if (!t.gemv_takes_k(K)) return fail(GGML_HIP_ERR_UNSUPPORTED, t.err_gemv_k);
+        HIP_RET(q45   ? ghip::gemv_q45_K(type == KQuant::Q5_K, w, K, M, x, N, y, ldy, g_dev[id].info, s)
+                : q23 ? ghip::gemv_q23_K(type == KQuant::Q3_K, w, K, M, x, N, y, ldy, g_dev[id].info, s)
+                      : ghip::gemv_q6_K(w, K, M, x, N, y, ldy, g_dev[id].info, s));
         return GGML_HIP_OK;
     }
-    if (algo != 4 && algo != 5) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1, 4 or 5");
+    if (!algo_ok) return bad_algo();                     // (Q6_K only: the others were refused above)
     void *ws = nullptr;
-    if (algo == 5) {
+    if (algo == t.gemm_algo) {
         if (too_many_tiles(M, N)) return fail(GGML_HIP_ERR_UNSUPPORTED, ERR_TILES);
-        const int wrc = stream_workspace(id, s, workspace_bytes_q6k_gemm(K, N), &ws);
+        const size_t dig_bytes = q45 ? (size_t)N * (size_t)(K / QK_K) * 16 : 0;
+        const int wrc = stream_workspace(id, s, workspace_bytes_kquant_gemm(K, N) + dig_bytes, &ws);
         if (wrc != GGML_HIP_OK) return wrc;
-        float *xd = (float *)((char *)ws + kquant_planes_offset(K, N));
-        HIP_RET(ghip::quantize_q8_K_planes(x, K, N, ws, xd, s));
-        HIP_RET(ghip::gemm_q6_K(w, K, M, ws, xd, N, y, ldy, s));
+        char *dig = (char *)ws + kquant_planes_offset(K, N);
+        float *xd = (float *)(dig + dig_bytes);
+        HIP_RET(ghip::quantize_q8_K_planes(x, K, N, ws, xd, q45 ? dig : nullptr, s));
+        HIP_RET(q45   ? ghip::gemm_q45_K(type == KQuant::Q5_K, w, K, M, ws, xd, dig, N, y, ldy, g_dev[id].info, s)
+                : q23 ? ghip::gemm_q23_K(type == KQuant::Q3_K, w, K, M, ws, xd, N, y, ldy, g_dev[id].info, s)
+                      : ghip::gemm_q6_K(w, K, M, ws, xd, N, y, ldy, g_dev[id].info, s));
         return GGML_HIP_OK;
     }
     const int wrc = quantize_q8k_ws(id, x, K, N, s, &ws);
     if (wrc != GGML_HIP_OK) return wrc;
-    HIP_RET(ghip::mm_exact_q6_K(w, K, M, ws, N, y, ldy, s));
+    HIP_RET(q45   ? ghip::mm_exact_q45_K(type == KQuant::Q5_K, w, K, M, ws, N, y, ldy, s)
+            : q23 ? ghip::mm_exact_q23_K(type == KQuant::Q3_K, w, K, M, ws, N, y, ldy, s)
+                  : ghip::mm_exact_q6_K(w, K, M, ws, N, y, ldy, s));
     return GGML_HIP_OK;
+}
+static int mul_mat_q6k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                           hipStream_t s) {
+    return mul_mat_kquant_dev(ROW_Q6_K, KQuant::Q6_K, w, K, M, x, N, y, ldy, algo, s);
+}
+static int mul_mat_q5k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                           hipStream_t s) {
+    return mul_mat_kquant_dev(ROW_Q5_K, KQuant::Q5_K, w, K, M, x, N, y, ldy, algo, s);
+}
+static int mul_mat_q4k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                           hipStream_t s) {
+    return mul_mat_kquant_dev(ROW_Q4_K, KQuant::Q4_K, w, K, M, x, N, y, ldy, algo, s);
+}
+static int mul_mat_q3k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                           hipStream_t s) {
+    return mul_mat_kquant_dev(ROW_Q3_K, KQuant::Q3_K, w, K, M, x, N, y, ldy, algo, s);
+}
+static int mul_mat_q2k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                           hipStream_t s) {
+    return mul_mat_kquant_dev(ROW_Q2_K, KQuant::Q2_K, w, K, M, x, N, y, ldy, algo, s);
 }
 
 // Q8_0 / Q4_1 / Q5_0 / Q5_1 (blk32_w.hip), one body over the four rows.  mn: the type has a minimum and q8_1
@@ -629,87 +665,6 @@ static int mul_mat_q5_0_dev(const void *w, int64_t K, int64_t M, const float *x,
 static int mul_mat_q5_1_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
                             hipStream_t s) {
     return mul_mat_blk32_dev(ROW_Q5_1, Blk32::Q5_1, w, K, M, x, N, y, ldy, algo, s);
-}
-
-// Q5_K (qh) / Q4_K (q45_k.hip, q45_k_gemm.hip): algo 6 = the q8_K values of x and their sub-block sums' digits as
-// planes in the workspace + k_gemm_q45_K (5 stays invalid for these types).  An algo the types reject is refused
-// before anything else, an empty call included.
-static int mul_mat_q45k_dev(bool qh, const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
-                            int algo, hipStream_t s) {
-    if (algo != 0 && algo != 1 && algo != 4 && algo != 6) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1, 4 or 6");
-    const WeightType &t = ROW_Q5_K;                      // (the two rows differ in the run function only)
-    const int rc = check_operands(t, w, K, M, x, N, y, ldy);
-    if (rc != GGML_HIP_OK || N == 0) return rc;
-    const int id = current_device();
-    if (algo == 0) algo = auto_algo(t, K, N);
-    if (algo == 1) {
-        if (!t.gemv_takes_k(K)) return fail(GGML_HIP_ERR_UNSUPPORTED, t.err_gemv_k);
-        HIP_RET(ghip::gemv_q45_K(qh, w, K, M, x, N, y, ldy, g_dev[id].info, s));
-        return GGML_HIP_OK;
-    }
-    void *ws = nullptr;
-    if (algo == 6) {
-        if (too_many_tiles(M, N)) return fail(GGML_HIP_ERR_UNSUPPORTED, ERR_TILES);
-        const int wrc = stream_workspace(id, s, workspace_bytes_q45k_gemm(K, N), &ws);
-        if (wrc != GGML_HIP_OK) return wrc;
-        void *dig = (char *)ws + kquant_planes_offset(K, N);
-        float *xd = (float *)((char *)dig + (size_t)N * (size_t)(K / QK_K) * 16);
-        HIP_RET(ghip::quantize_q8_K_digit_planes(x, K, N, ws, xd, dig, s));
-        HIP_RET(ghip::gemm_q45_K(qh, w, K, M, ws, xd, dig, N, y, ldy, g_dev[id].info, s));
-        return GGML_HIP_OK;
-    }
-    const int wrc = quantize_q8k_ws(id, x, K, N, s, &ws);
-    if (wrc != GGML_HIP_OK) return wrc;
-    HIP_RET(ghip::mm_exact_q45_K(qh, w, K, M, ws, N, y, ldy, s));
-    return GGML_HIP_OK;
-}
-static int mul_mat_q5k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
-                           hipStream_t s) {
-    return mul_mat_q45k_dev(true, w, K, M, x, N, y, ldy, algo, s);
-}
-static int mul_mat_q4k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
-                           hipStream_t s) {
-    return mul_mat_q45k_dev(false, w, K, M, x, N, y, ldy, algo, s);
-}
-
-// Q3_K (q3) / Q2_K (q23_k.hip, q23_k_gemm.hip): algo 8 = the q8_K values of x as planes in the workspace (the Q6_K
-// GEMM's quantizer and layout) + k_gemm_q23_K on the weights in place, any K % 256 == 0.  An algo the types reject is
-// refused before anything else, an empty call included.
-static int mul_mat_q23k_dev(bool q3, const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
-                            int algo, hipStream_t s) {
-    if (algo != 0 && algo != 1 && algo != 4 && algo != 8) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1, 4 or 8");
-    const WeightType &t = ROW_Q3_K;                      // (the two rows differ in the run function only)
-    const int rc = check_operands(t, w, K, M, x, N, y, ldy);
-    if (rc != GGML_HIP_OK || N == 0) return rc;
-    const int id = current_device();
-    if (algo == 0) algo = auto_algo(t, K, N);
-    if (algo == 1) {
-        if (!t.gemv_takes_k(K)) return fail(GGML_HIP_ERR_UNSUPPORTED, t.err_gemv_k);
-        HIP_RET(ghip::gemv_q23_K(q3, w, K, M, x, N, y, ldy, g_dev[id].info, s));
-        return GGML_HIP_OK;
-    }
-    void *ws = nullptr;
-    if (algo == 8) {
-        if (too_many_tiles(M, N)) return fail(GGML_HIP_ERR_UNSUPPORTED, ERR_TILES);
-        const int wrc = stream_workspace(id, s, workspace_bytes_q6k_gemm(K, N), &ws);
-        if (wrc != GGML_HIP_OK) return wrc;
-        float *xd = (float *)((char *)ws + kquant_planes_offset(K, N));
-        HIP_RET(ghip::quantize_q8_K_planes(x, K, N, ws, xd, s));
-        HIP_RET(ghip::gemm_q23_K(q3, w, K, M, ws, xd, N, y, ldy, g_dev[id].info, s));
-        return GGML_HIP_OK;
-    }
-    const int wrc = quantize_q8k_ws(id, x, K, N, s, &ws);
-    if (wrc != GGML_HIP_OK) return wrc;
-    HIP_RET(ghip::mm_exact_q23_K(q3, w, K, M, ws, N, y, ldy, s));
-    return GGML_HIP_OK;
-}
-static int mul_mat_q3k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
-                           hipStream_t s) {
-    return mul_mat_q23k_dev(true, w, K, M, x, N, y, ldy, algo, s);
-}
-static int mul_mat_q2k_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
-                           hipStream_t s) {
-    return mul_mat_q23k_dev(false, w, K, M, x, N, y, ldy, algo, s);
 }
 
 // F16 (f16_w.hip, ggml_ops.hip): algo 1 = k_gemv_f16w in column tiles; algo 4 = op_mul_mat_f16_f32's bitwise kernels

@@ -115,6 +115,17 @@ inline hipError_t raise_dynamic_lds(int bytes) {
     return e;
 }
 
+// the columns per workgroup (64, 128 or 256) of the int8-MFMA GEMMs that decode 64 weight rows in place per
+// workgroup.  One workgroup per CU (LDS), and with fit_rule a workgroup's time is mostly its per-superblock load and
+// decode, not its MFMAs: 256 columns only where the grid of 128-column tiles would not fit on the device at once
+// (256 CUs where the count is unknown).  Without it, 256 columns for every N > 128.  y does not depend on the choice.
+inline int gemm_tile_columns(int64_t M, int64_t N, int num_cus, bool fit_rule) {
+    if (N <= 64) return 64;
+    if (N <= 128) return 128;
+    const int64_t grid128 = ((M + 63) / 64) * ((N + 127) / 128);
+    return fit_rule && grid128 <= (int64_t)(num_cus > 0 ? num_cus : 256) ? 128 : 256;
+}
+
 // the 1-D launch of a quantizer or dequantizer: blocks of 256 threads, `per_block` of the `items` each; nothing
 // to do is success
 template <typename... P, typename... A>

@@ -46,7 +46,7 @@
 // sub-block, sums it (four v_dot4 against 0x01010101) and writes the two digit bytes to LDS.
 //
 // Tile: 64 rows x 32 WN TN columns, 2 x WN waves, each TN 32 x 32 MFMA tiles; the (WN, TN) set and the rule of
-// k_gemm_q45_K (at gemm_q23_K_t); MFMA A = x (D's register index = column), B = weights (D's lane = row), so d and
+// k_gemm_q45_K (gemm_tile_columns, launch.h); MFMA A = x (D's register index = column), B = weights (D's lane = row), so d and
 // dmin are one value each per lane and the y stores run along m.  Registers (256 per wave at two waves per SIMD):
 // the prefetched operands are at most 9 x 4 weight dwords and 8 x 4 of x, a tile's S, Mh, Ml 48, acc 16 TN.
 // LDS: the weight and x rows are 256 + 16 bytes, which spreads the 32 rows of an operand read (ds_read_b128, banks
@@ -62,16 +62,15 @@
 // its decode overlaps the other waves' MFMAs (measured 13-32 % less time than one stage on the LLaMA-7B layer
 // shapes, profiles/q23k_gemm.json against q23k_gemm_build1.json; y is the same).  Two stages of the 256-column
 // tile (2 x 97 KB) exceed the 160 KiB, so it keeps one stage and two barriers.
+#include "kquant_gemm.h"
 #include "q23_k_device.h"
 
 namespace ghip {
 
-static constexpr int G23_BM = 64;                      // rows per workgroup
-static constexpr int G23_LD = QK_K + 16;               // LDS row pitch of the int8 planes
 // an LDS stage of a BN-column tile: the weight and x planes, Q2_K's m bytes and digit bytes, d, dmin, d_x
 template <bool Q3>
 constexpr int G23_stage_bytes(int BN) {
-    return (G23_BM + BN) * G23_LD + (Q3 ? 0 : (G23_BM + 2 * BN) * 16) + (2 * G23_BM + BN) * 4;
+    return (KG_BM + BN) * KG_LD + (Q3 ? 0 : (KG_BM + 2 * BN) * 16) + (2 * KG_BM + BN) * 4;
 }
 constexpr int G23_stages(int TN) { return TN == 1 ? 2 : 1; }     // two stages of the 256-column tile exceed the LDS
 
@@ -92,27 +91,27 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q23_K(const uint8_t *__restri
     constexpr int BS = Q23<Q3>::BYTES;
     constexpr int THREADS = 128 * WN;                  // 2 x WN waves
     constexpr int BN = 32 * WN * TN;                   // columns per workgroup
-    constexpr int NP = G23_BM / (8 * WN);              // passes of four rows a wave decodes per superblock
+    constexpr int NP = KG_BM / (8 * WN);              // passes of four rows a wave decodes per superblock
     constexpr int XP = BN * 16 / THREADS;              // 16-byte pieces of the x tile per thread (4 TN)
     constexpr int NW = Q3 ? 9 : 5;                     // a lane's weight dwords per pass (Gemv23Regs' of q23_k.hip)
     constexpr int DG = Q3 ? 0 : 16;                    // bytes of m per row / of each bsum16 digit per column
     constexpr int SB = G23_stage_bytes<Q3>(BN);        // one LDS stage
     constexpr int NS = G23_stages(TN);                 // stages: two where they fit (header)
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint8_t *wq = smem;                                // [64][G23_LD]  the scaled weights
-    uint8_t *xs = wq + G23_BM * G23_LD;                // [BN][G23_LD]
-    uint8_t *ms = xs + BN * G23_LD;                    // [64][16]   m[0..15]       (Q2_K)
-    uint8_t *xdl = ms + G23_BM * DG;                   // [BN][16]   bl[0..15]      (Q2_K)
+    uint8_t *wq = smem;                                // [64][KG_LD]  the scaled weights
+    uint8_t *xs = wq + KG_BM * KG_LD;                // [BN][KG_LD]
+    uint8_t *ms = xs + BN * KG_LD;                    // [64][16]   m[0..15]       (Q2_K)
+    uint8_t *xdl = ms + KG_BM * DG;                   // [BN][16]   bl[0..15]      (Q2_K)
     uint8_t *xdh = xdl + BN * DG;                      // [BN][16]   bh[0..15]      (Q2_K)
     float *dws = reinterpret_cast<float *>(xdh + BN * DG);     // [64]
-    float *dmws = dws + G23_BM;                        // [64]       (Q2_K)
-    float *dxs = dmws + G23_BM;                        // [BN]
+    float *dmws = dws + KG_BM;                        // [64]       (Q2_K)
+    float *dxs = dmws + KG_BM;                        // [BN]
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // the column tiles of one row tile are neighbours in the grid (they share the weight rows)
     const int mt = (int)(blockIdx.x / (unsigned)ntn), nt = (int)(blockIdx.x - (unsigned)mt * (unsigned)ntn);
-    const int m0 = mt * G23_BM, n0 = nt * BN;
+    const int m0 = mt * KG_BM, n0 = nt * BN;
     const int K = nb * QK_K;
     const int64_t rowbytes = (int64_t)nb * BS;
 
@@ -192,7 +191,7 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q23_K(const uint8_t *__restri
                 q23_values<Q3>(a[0], 0u, n4, v);
                 q2_scales(a[1], a[2], h4, sc);
             }
-            uint8_t *o = wq + so + r * G23_LD + 128 * n4 + 4 * i;
+            uint8_t *o = wq + so + r * KG_LD + 128 * n4 + 4 * i;
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const uint32_t s = Q3 ? (uint32_t)(-sc[k]) & 0xFFu : (uint32_t)sc[k];
@@ -212,7 +211,7 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q23_K(const uint8_t *__restri
 #pragma unroll
         for (int p = 0; p < XP; p++) {
             const int pp = tid + THREADS * p;
-            *reinterpret_cast<u32x4 *>(xs + so + (pp >> 4) * G23_LD + (pp & 15) * 16) = g.x[p];
+            *reinterpret_cast<u32x4 *>(xs + so + (pp >> 4) * KG_LD + (pp & 15) * 16) = g.x[p];
             if constexpr (!Q3) {
                 // the piece is sub-block pp % 16 of column pp / 16: its bsum16 in [-2048, 2032] as two digits
                 int s16 = __builtin_amdgcn_sdot4((int)g.x[p].x, 0x01010101, 0, false);
@@ -228,8 +227,8 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q23_K(const uint8_t *__restri
 
     const int wr = wave & 1, wt = wave >> 1;
     const int c = lane & 31, h = lane >> 5;
-    const uint8_t *b_p = wq + (32 * wr + c) * G23_LD + 16 * h;
-    const uint8_t *a_p = xs + (32 * TN * wt + c) * G23_LD + 16 * h;
+    const uint8_t *b_p = wq + (32 * wr + c) * KG_LD + 16 * h;
+    const uint8_t *a_p = xs + (32 * TN * wt + c) * KG_LD + 16 * h;
     const i32x16 iz = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     float acc[TN][16];
 #pragma unroll
@@ -260,13 +259,14 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q23_K(const uint8_t *__restri
             i32x16 S = iz;
 #pragma unroll
             for (int s = 0; s < QK_K / 32; s++) {
-                const i32x4 a = *reinterpret_cast<const i32x4 *>(a_p + so + 32 * tt * G23_LD + 32 * s);
+                const i32x4 a = *reinterpret_cast<const i32x4 *>(a_p + so + 32 * tt * KG_LD + 32 * s);
                 const i32x4 bw = *reinterpret_cast<const i32x4 *>(b_p + so + 32 * s);
                 S = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bw, S, 0, 0, 0);
             }
             // the superblock's fp32 step per output: the GEMV's, in the GEMV's order
 #pragma unroll
             for (int e = 0; e < 16; e++) {
+                // (kquant_col's sum written out: through the function Q2_K's 256-column tile compiles to another schedule)
                 const float dx = dxp[32 * TN * wt + 32 * tt + (e & 3) + 8 * (e >> 2) + 4 * h];
                 float tb;
                 if constexpr (Q3) {
@@ -316,40 +316,23 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q23_K(const uint8_t *__restri
         for (int tt = 0; tt < TN; tt++)
 #pragma unroll
             for (int e = 0; e < 16; e++) {
-                const int n = n0 + 32 * TN * wt + 32 * tt + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int n = kquant_col(n0 + 32 * TN * wt + 32 * tt, e, h);
                 if (n < N) y[(int64_t)n * ldy + row] = acc[tt][e];
             }
     }
 }
 
-template <bool Q3, int WN, int TN>
-static hipError_t launch_gemm23(const uint8_t *W, int nb, int M, const uint8_t *xqs, const float *xd, int N, float *y,
-                                int64_t ldy, hipStream_t s) {
-    constexpr int BN = 32 * WN * TN;
-    constexpr size_t lds = (size_t)G23_stages(TN) * G23_stage_bytes<Q3>(BN);
-    if (const hipError_t e = raise_dynamic_lds<k_gemm_q23_K<Q3, WN, TN>>((int)lds); e != hipSuccess) return e;
-    const int64_t ntm = ((int64_t)M + G23_BM - 1) / G23_BM, ntn = ((int64_t)N + BN - 1) / BN;
-    if (ntm * ntn >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-    (void)hipGetLastError();  // report only this launch's error
-    launch_k(k_gemm_q23_K<Q3, WN, TN>, dim3((unsigned)(ntm * ntn)), dim3(128 * WN), lds, s, W, nb, M, xqs, xd, N, (int)ntn,
-             y, ldy);
-    return hipGetLastError();
-}
-
 template <bool Q3>
 static hipError_t gemm_q23_K_t(const void *W, int64_t K, int64_t M, const void *xqs, const float *xd, int64_t N, float *y,
                                int64_t ldy, int num_cus, hipStream_t s) {
-    if (K <= 0 || K % QK_K || M < 1 || M >= ((int64_t)1 << 31) || N < 1 || N * K >= ((int64_t)1 << 31))
-        return hipErrorInvalidValue;
-    const int nb = (int)(K / QK_K);
-    const uint8_t *w = (const uint8_t *)W, *q = (const uint8_t *)xqs;
-    if (N <= 64) return launch_gemm23<Q3, 2, 1>(w, nb, (int)M, q, xd, (int)N, y, ldy, s);
-    // k_gemm_q45_K's rule: 256 columns per tile only where the grid of 128-column tiles would not fit on the device
-    // at once (y does not depend on this choice)
-    const int64_t grid128 = ((M + G23_BM - 1) / G23_BM) * ((N + 127) / 128);
-    if (N <= 128 || grid128 <= (int64_t)(num_cus > 0 ? num_cus : 256))
-        return launch_gemm23<Q3, 4, 1>(w, nb, (int)M, q, xd, (int)N, y, ldy, s);
-    return launch_gemm23<Q3, 4, 2>(w, nb, (int)M, q, xd, (int)N, y, ldy, s);
+    return with_kquant_tile(K, M, N, num_cus, true, [&](auto wn, auto tn, int nb) {
+        constexpr int WN = decltype(wn)::value, TN = decltype(tn)::value, BN = 32 * WN * TN;
+        constexpr size_t lds = (size_t)G23_stages(TN) * G23_stage_bytes<Q3>(BN);
+        return launch_gemm_kquant<k_gemm_q23_K<Q3, WN, TN>, WN, TN>(lds, M, N, [&](dim3 grid, dim3 block, int ntn) {
+            launch_k(k_gemm_q23_K<Q3, WN, TN>, grid, block, lds, s, (const uint8_t *)W, nb, (int)M, (const uint8_t *)xqs,
+                     xd, (int)N, ntn, y, ldy);
+        });
+    });
 }
 
 // y[n * ldy + m] = W[m] . x[n] on the planes quantize_q8_K_planes wrote; any K % 256 == 0, M, N >= 1

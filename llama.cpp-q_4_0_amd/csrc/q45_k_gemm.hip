@@ -30,11 +30,11 @@
 // load inside the matrix.  Rows >= M and columns >= N of a ragged tile read the last row / column (inside the
 // operands) and are never stored.  x is the q8_K quantization (q8k_block_lane, the GEMV prologue's bits) written
 // once per call as planes: qs int8 [N][K], d f32 [N][K / 256] and dig int8 [N][K / 256][16], the eight bl then
-// the eight bh of the (token, superblock)'s bsum32 (k_quantize_q8_K_digit_planes).
+// the eight bh of the (token, superblock)'s bsum32 (k_quantize_q8_K_planes<true>, kquant_gemm.h).
 //
 // Tile: 64 rows x 32 WN TN columns, 2 x WN waves, each TN 32 x 32 MFMA tiles ((WN, TN) = (2, 1) up to N = 64,
 // (4, 1) up to 128 and wherever its grid still fits on the device at once, else (4, 2): the set of k_gemm_q6_K;
-// the rule is at gemm_q45_K_t); MFMA A = x (D's register index = column), B = weights
+// the rule is gemm_tile_columns, launch.h); MFMA A = x (D's register index = column), B = weights
 // (D's lane = row), so d and dmin are one value each per lane and the y stores run along m.  Registers: a wave has
 // 256 at two waves per SIMD (launch bound 512), and at TN = 2 the prefetched operands take about 60 of them, so
 // a wave finishes one 32 x 32 tile (H, L, Mh, Ml: 64) before it starts the next; acc is 16 TN.
@@ -45,38 +45,10 @@
 // issue cycles for 2 array cycles anyway.  The m bytes and the bsum32 digits are 8 bytes per row / column
 // (ds_read_b64, 32 lanes on 64 distinct banks).  One superblock per stage in a single LDS buffer; the next
 // superblock's global loads are issued before the current one's MFMAs.
+#include "kquant_gemm.h"
 #include "q45_k_device.h"
 
 namespace ghip {
-
-static constexpr int G45_BM = 64;                      // rows per workgroup
-static constexpr int G45_LD = QK_K + 16;               // LDS row pitch of the int8 planes
-
-// x f32 [N][K] -> qs int8 [N][K] + d f32 [N][K / 256] + dig int8 [N][K / 256][16]; one wave per block, the values
-// of the GEMV prologue (q8k_block_lane, group8_sum of the lane's four q8)
-__global__ __launch_bounds__(256) void k_quantize_q8_K_digit_planes(const float *__restrict__ x, int64_t nblocks,
-                                                                     uint32_t *__restrict__ qs, float *__restrict__ xd,
-                                                                     int8_t *__restrict__ dig) {
-    const int lane = threadIdx.x & 63;
-    const int64_t blk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (blk >= nblocks) return;                      // wave-uniform
-    const float4 v = reinterpret_cast<const float4 *>(x)[blk * 64 + lane];
-    float d;
-    const uint32_t p = q8k_block_lane(v, lane, d);
-    qs[blk * 64 + lane] = p;
-    const int s32 = group8_sum(__builtin_amdgcn_sdot4((int)p, 0x01010101, 0, false));   // [-4096, 4064]
-    if ((lane & 7) == 0) {
-        dig[blk * 16 + (lane >> 3)] = (int8_t)(s32 & 127);
-        dig[blk * 16 + 8 + (lane >> 3)] = (int8_t)(s32 >> 7);
-    }
-    if (lane == 0) xd[blk] = d;
-}
-
-hipError_t quantize_q8_K_digit_planes(const float *x, int64_t K, int64_t N, void *qs, float *xd, void *dig,
-                                      hipStream_t s) {
-    const int64_t nblocks = N * (K / QK_K);
-    return launch_1d(k_quantize_q8_K_digit_planes, nblocks, 4, s, x, nblocks, (uint32_t *)qs, xd, (int8_t *)dig);
-}
 
 // four 4- or 5-bit values (one per byte) and their sub-block's scale (<= 63) -> the int8 digits of w' = sc q =
 // 128 hi + lo, packed in element order.  Elements 0, 2 and 1, 3 go through 16-bit fields of one 24-bit multiply:
@@ -95,24 +67,24 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q45_K(const uint8_t *__restri
     constexpr int BS = Q45<QH>::BYTES, QS = Q45<QH>::QS;
     constexpr int THREADS = 128 * WN;                  // 2 x WN waves
     constexpr int BN = 32 * WN * TN;                   // columns per workgroup
-    constexpr int NP = G45_BM / (4 * WN);              // row pairs a wave decodes per superblock (half a wave per row)
+    constexpr int NP = KG_BM / (4 * WN);              // row pairs a wave decodes per superblock (half a wave per row)
     constexpr int XP = BN * 16 / THREADS;              // 16-byte pieces of the x tile per thread (4 TN)
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint8_t *whi = smem;                               // [64][G45_LD]
-    uint8_t *wlo = whi + G45_BM * G45_LD;              // [64][G45_LD]
-    uint8_t *xs = wlo + G45_BM * G45_LD;               // [BN][G45_LD]
-    uint8_t *ms = xs + BN * G45_LD;                    // [64][8]   m[0..7]
-    uint8_t *xdl = ms + G45_BM * 8;                    // [BN][8]   bl[0..7]
+    uint8_t *whi = smem;                               // [64][KG_LD]
+    uint8_t *wlo = whi + KG_BM * KG_LD;              // [64][KG_LD]
+    uint8_t *xs = wlo + KG_BM * KG_LD;               // [BN][KG_LD]
+    uint8_t *ms = xs + BN * KG_LD;                    // [64][8]   m[0..7]
+    uint8_t *xdl = ms + KG_BM * 8;                    // [BN][8]   bl[0..7]
     uint8_t *xdh = xdl + BN * 8;                       // [BN][8]   bh[0..7]
     float *dws = reinterpret_cast<float *>(xdh + BN * 8);      // [64]
-    float *dmws = dws + G45_BM;                        // [64]
-    float *dxs = dmws + G45_BM;                        // [BN]
+    float *dmws = dws + KG_BM;                        // [64]
+    float *dxs = dmws + KG_BM;                        // [BN]
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // the column tiles of one row tile are neighbours in the grid (they share the weight rows)
     const int mt = (int)(blockIdx.x / (unsigned)ntn), nt = (int)(blockIdx.x - (unsigned)mt * (unsigned)ntn);
-    const int m0 = mt * G45_BM, n0 = nt * BN;
+    const int m0 = mt * KG_BM, n0 = nt * BN;
     const int K = nb * QK_K;
     const int64_t rowbytes = (int64_t)nb * BS;
 
@@ -128,9 +100,9 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q45_K(const uint8_t *__restri
     }
     int xoff[XP];
 #pragma unroll
-    for (int p = 0; p < XP; p++) {
-        const int pp = tid + THREADS * p, n = n0 + (pp >> 4);
-        xoff[p] = (n < N ? n : N - 1) * K + (pp & 15) * 16;            // N K < 2^31 (host check)
+    for (int ii = 0; ii < XP; ii++) {
+        const int p = tid + THREADS * ii, n = n0 + (p >> 4);
+        xoff[ii] = (n < N ? n : N - 1) * K + (p & 15) * 16;             // N K < 2^31 (host check)
     }
     const int dn = n0 + (tid & (BN - 1));
     const int dxoff = (dn < N ? dn : N - 1) * nb;
@@ -170,7 +142,7 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q45_K(const uint8_t *__restri
             uint32_t h0, l0, h1, l1;
             q45_digits(qlo, scw & 0xFFu, h0, l0);
             q45_digits(qhi, (scw >> 8) & 0xFFu, h1, l1);
-            const int o = r * G45_LD + 64 * j + 4 * i;
+            const int o = r * KG_LD + 64 * j + 4 * i;
             *reinterpret_cast<uint32_t *>(whi + o) = h0;
             *reinterpret_cast<uint32_t *>(whi + o + 32) = h1;
             *reinterpret_cast<uint32_t *>(wlo + o) = l0;
@@ -184,7 +156,7 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q45_K(const uint8_t *__restri
 #pragma unroll
         for (int p = 0; p < XP; p++) {
             const int pp = tid + THREADS * p;
-            *reinterpret_cast<u32x4 *>(xs + (pp >> 4) * G45_LD + (pp & 15) * 16) = g.x[p];
+            *reinterpret_cast<u32x4 *>(xs + (pp >> 4) * KG_LD + (pp & 15) * 16) = g.x[p];
         }
         if (tid < BN) {
             *reinterpret_cast<u32x2 *>(xdl + 8 * tid) = u32x2{g.dig.x, g.dig.y};
@@ -195,9 +167,9 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q45_K(const uint8_t *__restri
 
     const int wr = wave & 1, wt = wave >> 1;
     const int c = lane & 31, h = lane >> 5;
-    const uint8_t *bh_p = whi + (32 * wr + c) * G45_LD + 16 * h;
-    const uint8_t *bl_p = wlo + (32 * wr + c) * G45_LD + 16 * h;
-    const uint8_t *a_p = xs + (32 * TN * wt + c) * G45_LD + 16 * h;
+    const uint8_t *bh_p = whi + (32 * wr + c) * KG_LD + 16 * h;
+    const uint8_t *bl_p = wlo + (32 * wr + c) * KG_LD + 16 * h;
+    const uint8_t *a_p = xs + (32 * TN * wt + c) * KG_LD + 16 * h;
     const i32x16 iz = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     float acc[TN][16];
 #pragma unroll
@@ -231,7 +203,7 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q45_K(const uint8_t *__restri
             i32x16 H = iz, L = iz;
 #pragma unroll
             for (int s = 0; s < QK_K / 32; s++) {
-                const i32x4 a = *reinterpret_cast<const i32x4 *>(a_p + 32 * tt * G45_LD + 32 * s);
+                const i32x4 a = *reinterpret_cast<const i32x4 *>(a_p + 32 * tt * KG_LD + 32 * s);
                 const i32x4 bh = *reinterpret_cast<const i32x4 *>(bh_p + 32 * s);
                 const i32x4 bl = *reinterpret_cast<const i32x4 *>(bl_p + 32 * s);
                 H = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bh, H, 0, 0, 0);
@@ -240,7 +212,7 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q45_K(const uint8_t *__restri
             // the superblock's fp32 step per output: the GEMV's, in the GEMV's order
 #pragma unroll
             for (int e = 0; e < 16; e++) {
-                const float dx = dxs[32 * TN * wt + 32 * tt + (e & 3) + 8 * (e >> 2) + 4 * h];
+                const float dx = dxs[kquant_col(32 * TN * wt + 32 * tt, e, h)];
                 const int msum = Mh[e] * 128 + Ml[e], isum = H[e] * 128 + L[e];
                 const float negp = -__fmul_rn(__fmul_rn(dx, dmw), (float)msum);
                 const float tb = __builtin_fmaf(__fmul_rn(dx, dw), (float)isum, negp);
@@ -252,47 +224,29 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q45_K(const uint8_t *__restri
     const int row = m0 + 32 * wr + c;
     if (row < M) {
 #pragma unroll
-        for (int tt = 0; tt < TN; tt++)
+        for (int t = 0; t < TN; t++)
 #pragma unroll
             for (int e = 0; e < 16; e++) {
-                const int n = n0 + 32 * TN * wt + 32 * tt + (e & 3) + 8 * (e >> 2) + 4 * h;
-                if (n < N) y[(int64_t)n * ldy + row] = acc[tt][e];
+                const int n = kquant_col(n0 + 32 * TN * wt + 32 * t, e, h);
+                if (n < N) y[(int64_t)n * ldy + row] = acc[t][e];
             }
     }
-}
-
-template <bool QH, int WN, int TN>
-static hipError_t launch_gemm45(const uint8_t *W, int nb, int M, const uint8_t *xqs, const float *xd, const uint8_t *xdig,
-                                int N, float *y, int64_t ldy, hipStream_t s) {
-    constexpr int BN = 32 * WN * TN;
-    constexpr size_t lds = (size_t)(2 * G45_BM + BN) * G45_LD + (size_t)(G45_BM + 2 * BN) * 8 + (size_t)(2 * G45_BM + BN) * 4;
-    if (const hipError_t e = raise_dynamic_lds<k_gemm_q45_K<QH, WN, TN>>((int)lds); e != hipSuccess) return e;
-    const int64_t ntm = ((int64_t)M + G45_BM - 1) / G45_BM, ntn = ((int64_t)N + BN - 1) / BN;
-    if (ntm * ntn >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-    (void)hipGetLastError();  // report only this launch's error
-    launch_k(k_gemm_q45_K<QH, WN, TN>, dim3((unsigned)(ntm * ntn)), dim3(128 * WN), lds, s, W, nb, M, xqs, xd, xdig, N,
-             (int)ntn, y, ldy);
-    return hipGetLastError();
 }
 
 template <bool QH>
 static hipError_t gemm_q45_K_t(const void *W, int64_t K, int64_t M, const void *xqs, const float *xd, const void *xdig,
                                int64_t N, float *y, int64_t ldy, int num_cus, hipStream_t s) {
-    if (K <= 0 || K % QK_K || M < 1 || M >= ((int64_t)1 << 31) || N < 1 || N * K >= ((int64_t)1 << 31))
-        return hipErrorInvalidValue;
-    const int nb = (int)(K / QK_K);
-    const uint8_t *w = (const uint8_t *)W, *q = (const uint8_t *)xqs, *dg = (const uint8_t *)xdig;
-    if (N <= 64) return launch_gemm45<QH, 2, 1>(w, nb, (int)M, q, xd, dg, (int)N, y, ldy, s);
-    // one workgroup per CU (LDS), and a workgroup's time is mostly its per-superblock load and decode, not its
-    // MFMAs: 256 columns per tile only where the grid of 128-column tiles would not fit on the device at once
-    // (y does not depend on this choice)
-    const int64_t grid128 = ((M + G45_BM - 1) / G45_BM) * ((N + 127) / 128);
-    if (N <= 128 || grid128 <= (int64_t)(num_cus > 0 ? num_cus : 256))
-        return launch_gemm45<QH, 4, 1>(w, nb, (int)M, q, xd, dg, (int)N, y, ldy, s);
-    return launch_gemm45<QH, 4, 2>(w, nb, (int)M, q, xd, dg, (int)N, y, ldy, s);
+    return with_kquant_tile(K, M, N, num_cus, true, [&](auto wn, auto tn, int nb) {
+        constexpr int WN = decltype(wn)::value, TN = decltype(tn)::value, BN = 32 * WN * TN;
+        constexpr size_t lds = (size_t)(2 * KG_BM + BN) * KG_LD + (size_t)(KG_BM + 2 * BN) * 8 + (size_t)(2 * KG_BM + BN) * 4;
+        return launch_gemm_kquant<k_gemm_q45_K<QH, WN, TN>, WN, TN>(lds, M, N, [&](dim3 grid, dim3 block, int ntn) {
+            launch_k(k_gemm_q45_K<QH, WN, TN>, grid, block, lds, s, (const uint8_t *)W, nb, (int)M, (const uint8_t *)xqs,
+                     xd, (const uint8_t *)xdig, (int)N, ntn, y, ldy);
+        });
+    });
 }
 
-// y[n * ldy + m] = W[m] . x[n] on the planes quantize_q8_K_digit_planes wrote; any K % 256 == 0, M, N >= 1
+// y[n * ldy + m] = W[m] . x[n] on the planes quantize_q8_K_planes wrote with dig; any K % 256 == 0, M, N >= 1
 hipError_t gemm_q45_K(bool qh, const void *W, int64_t K, int64_t M, const void *xqs, const float *xd, const void *xdig,
                       int64_t N, float *y, int64_t ldy, const DeviceInfo &dev, hipStream_t s) {
     return qh ? gemm_q45_K_t<true>(W, K, M, xqs, xd, xdig, N, y, ldy, dev.num_cus, s)

@@ -152,12 +152,6 @@ hipError_t gemv_q6_K(const void *W, int64_t K, int64_t M, const float *x, int64_
 // exact mode: y bit-identical to the AVX2 ggml_vec_dot_q6_K_q8_K on the pre-quantized xq8k; any N
 hipError_t mm_exact_q6_K(const void *W, int64_t K, int64_t M, const void *xq8k, int64_t N, float *y, int64_t ldy,
                          hipStream_t s);
-// prefill (q6_k_gemm.hip): the q8_K values of x as planes, qs int8 [N][K] (16-byte aligned) + d f32 [N][K / 256],
-// and the int8-MFMA GEMM on them, y bitwise gemv_q6_K's; any K % 256 == 0 (N K < 2^31), M, N >= 1
-hipError_t quantize_q8_K_planes(const float *x, int64_t K, int64_t N, void *qs, float *xd, hipStream_t s);
-hipError_t gemm_q6_K(const void *W, int64_t K, int64_t M, const void *xqs, const float *xd, int64_t N, float *y,
-                     int64_t ldy, hipStream_t s);
-
 // Q8_0 weights (blk32_w.hip): the layer matrices of a "mostly Q8_0" file.  W: ggml block_q8_0 rows, verbatim
 // (34 bytes per 32 weights, rows 4-byte aligned: K % 64 == 0).
 hipError_t dequantize_q8_0(const void *wq, int64_t K, int64_t M, float *w, hipStream_t s);
@@ -186,14 +180,6 @@ hipError_t gemv_q45_K(bool qh, const void *W, int64_t K, int64_t M, const float 
 // exact mode: y bit-identical to the AVX2 ggml_vec_dot_q5_K_q8_K / _q4_K_q8_K on the pre-quantized xq8k; any N
 hipError_t mm_exact_q45_K(bool qh, const void *W, int64_t K, int64_t M, const void *xq8k, int64_t N, float *y,
                           int64_t ldy, hipStream_t s);
-// prefill (q45_k_gemm.hip): the q8_K values of x as planes, qs int8 [N][K] + d f32 [N][K / 256] + dig int8
-// [N][K / 256][16] (the low then the high base-128 digits of the eight per-32 sums; qs and dig 16-byte aligned), and
-// the int8-MFMA GEMM on them, y bitwise gemv_q45_K's; any K % 256 == 0 (N K < 2^31), M, N >= 1
-hipError_t quantize_q8_K_digit_planes(const float *x, int64_t K, int64_t N, void *qs, float *xd, void *dig,
-                                      hipStream_t s);
-hipError_t gemm_q45_K(bool qh, const void *W, int64_t K, int64_t M, const void *xqs, const float *xd, const void *xdig,
-                      int64_t N, float *y, int64_t ldy, const DeviceInfo &dev, hipStream_t s);
-
 // Q3_K / Q2_K (q23_k.hip): the layer matrices of a "mostly Q3_K" / "mostly Q2_K" file.  W: ggml block_q3_K (110 bytes
 // per 256 weights) or block_q2_K (84 bytes) rows, verbatim, the matrix 4-byte aligned (a Q3_K block is then only
 // 2-byte aligned; no byte outside the matrix is read); q3: true Q3_K, false Q2_K.
@@ -207,8 +193,17 @@ hipError_t gemv_q23_K(bool q3, const void *W, int64_t K, int64_t M, const float 
 // exact mode: y bit-identical to the AVX2 ggml_vec_dot_q3_K_q8_K / _q2_K_q8_K on the pre-quantized xq8k; any N
 hipError_t mm_exact_q23_K(bool q3, const void *W, int64_t K, int64_t M, const void *xq8k, int64_t N, float *y,
                           int64_t ldy, hipStream_t s);
-// prefill (q23_k_gemm.hip): the int8-MFMA GEMM on the planes of quantize_q8_K_planes, the blocks read in place, y
-// bitwise gemv_q23_K's; any K % 256 == 0 (N K < 2^31), M, N >= 1
+
+// prefill of the five k-quants (q6_k_gemm.hip, q45_k_gemm.hip, q23_k_gemm.hip; what they share is kquant_gemm.h).
+// The q8_K values of x as planes: qs int8 [N][K] (16-byte aligned) + d f32 [N][K / 256], and where dig is not null
+// (Q5_K / Q4_K) dig int8 [N][K / 256][16], 16-byte aligned: the low then the high base-128 digits of the eight per-32
+// sums.  The int8-MFMA GEMMs on them, the blocks read in place, y bitwise the type's GEMV's; any K % 256 == 0
+// (N K < 2^31), M, N >= 1.
+hipError_t quantize_q8_K_planes(const float *x, int64_t K, int64_t N, void *qs, float *xd, void *dig, hipStream_t s);
+hipError_t gemm_q6_K(const void *W, int64_t K, int64_t M, const void *xqs, const float *xd, int64_t N, float *y,
+                     int64_t ldy, const DeviceInfo &dev, hipStream_t s);
+hipError_t gemm_q45_K(bool qh, const void *W, int64_t K, int64_t M, const void *xqs, const float *xd, const void *xdig,
+                      int64_t N, float *y, int64_t ldy, const DeviceInfo &dev, hipStream_t s);
 hipError_t gemm_q23_K(bool q3, const void *W, int64_t K, int64_t M, const void *xqs, const float *xd, int64_t N, float *y,
                       int64_t ldy, const DeviceInfo &dev, hipStream_t s);
 

@@ -24,8 +24,8 @@
 // (the block loop ends at the stage's count).  Rows >= M and columns >= N of a ragged tile read the last row /
 // column (inside the operands) and are never stored.
 //
-// Tile: 64 rows x 32 WN TN columns, 2 x WN waves, each TN 32 x 32 MFMA tiles, (WN, TN) by the rule of k_gemm_q45_K
-// (gemm_q5x1_t); MFMA A = x (D's register index = column), B = weights (D's lane = row), so d_w and m_w are one
+// Tile: 64 rows x 32 WN TN columns, 2 x WN waves, each TN 32 x 32 MFMA tiles, (WN, TN) by gemm_tile_columns' fit rule
+// (launch.h); MFMA A = x (D's register index = column), B = weights (D's lane = row), so d_w and m_w are one
 // value each per lane and block and the y stores run along m.  LDS: the int8 rows are 256 + 16 bytes (row c starts
 // at bank 4c mod 64: the 32 rows of a ds_read_b128 operand read spread over all banks); d_w / m_w are [8][64] and
 // d_x / s_x [8][BN] f32, block-major, so a lane's d_w is conflict-free and the four columns of a D register group
@@ -227,13 +227,11 @@ static hipError_t gemm_q5x1_t(const void *W, int64_t K, int64_t M, const int8_t 
         return hipErrorInvalidValue;
     const int nb = (int)(K / 32);
     const uint8_t *w = (const uint8_t *)W, *q = (const uint8_t *)xqs;
-    if (N <= 64) return launch_gemm5x1<QH, 2, 1>(w, nb, (int)M, q, xd, xsum, (int)N, y, ldy, s);
-    // k_gemm_q45_K's rule: 256 columns per tile only where the grid of 128-column tiles would not fit on the device
-    // at once (y does not depend on this choice)
-    const int64_t grid128 = ((M + G5G_BM - 1) / G5G_BM) * ((N + 127) / 128);
-    if (N <= 128 || grid128 <= (int64_t)(num_cus > 0 ? num_cus : 256))
-        return launch_gemm5x1<QH, 4, 1>(w, nb, (int)M, q, xd, xsum, (int)N, y, ldy, s);
-    return launch_gemm5x1<QH, 4, 2>(w, nb, (int)M, q, xd, xsum, (int)N, y, ldy, s);
+    switch (gemm_tile_columns(M, N, num_cus, true)) {
+        case 64: return launch_gemm5x1<QH, 2, 1>(w, nb, (int)M, q, xd, xsum, (int)N, y, ldy, s);
+        case 128: return launch_gemm5x1<QH, 4, 1>(w, nb, (int)M, q, xd, xsum, (int)N, y, ldy, s);
+        default: return launch_gemm5x1<QH, 4, 2>(w, nb, (int)M, q, xd, xsum, (int)N, y, ldy, s);
+    }
 }
 
 // y[n * ldy + m] = W[m] . x[n] on the planes quantize_q8_1_soa wrote (qs 16-byte, d and s 8-byte aligned); any

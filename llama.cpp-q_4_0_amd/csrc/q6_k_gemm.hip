@@ -26,31 +26,17 @@
 // registers are 16 columns of ONE row, so d_w is one value per lane and the y stores run along m.  LDS rows are
 // 256 + 16 bytes, which spreads the 32 rows of an operand read (16 bytes per lane) over all banks.  One superblock
 // per stage in a single LDS buffer; the next superblock's global loads are issued before the current one's MFMAs.
-#include "q6_k_device.h"
+#include "kquant_gemm.h"
 
 namespace ghip {
 
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 
-static constexpr int G6_BM = 64;                       // rows per workgroup
-static constexpr int G6_LD = QK_K + 16;                // LDS row pitch of the int8 planes
-
-// x f32 [N][K] -> qs int8 [N][K] + d f32 [N][K / 256]; one wave per block, the values of k_quantize_q8_K
-__global__ __launch_bounds__(256) void k_quantize_q8_K_planes(const float *__restrict__ x, int64_t nblocks,
-                                                               uint32_t *__restrict__ qs, float *__restrict__ xd) {
-    const int lane = threadIdx.x & 63;
-    const int64_t blk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (blk >= nblocks) return;                      // wave-uniform
-    const float4 v = reinterpret_cast<const float4 *>(x)[blk * 64 + lane];
-    float d;
-    const uint32_t p = q8k_block_lane(v, lane, d);
-    qs[blk * 64 + lane] = p;
-    if (lane == 0) xd[blk] = d;
-}
-
-hipError_t quantize_q8_K_planes(const float *x, int64_t K, int64_t N, void *qs, float *xd, hipStream_t s) {
+// x as the planes of kquant_gemm.h; dig null: none (only Q5_K / Q4_K read one)
+hipError_t quantize_q8_K_planes(const float *x, int64_t K, int64_t N, void *qs, float *xd, void *dig, hipStream_t s) {
     const int64_t nblocks = N * (K / QK_K);
-    return launch_1d(k_quantize_q8_K_planes, nblocks, 4, s, x, nblocks, (uint32_t *)qs, xd);
+    if (dig) return launch_1d(k_quantize_q8_K_planes<true>, nblocks, 4, s, x, nblocks, (uint32_t *)qs, xd, (int8_t *)dig);
+    return launch_1d(k_quantize_q8_K_planes<false>, nblocks, 4, s, x, nblocks, (uint32_t *)qs, xd, (int8_t *)nullptr);
 }
 
 // four 6-bit values (one per byte) and their scale -> the int8 digits of w' = sc (q - 32) = 128 hi + lo, packed
@@ -82,20 +68,20 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q6_K(const uint8_t *__restric
                                                          int N, int ntn, float *__restrict__ y, int64_t ldy) {
     constexpr int THREADS = 128 * WN;                  // 2 x WN waves
     constexpr int BN = 32 * WN * TN;                   // columns per workgroup
-    constexpr int RPW = G6_BM / (2 * WN);              // rows a wave decodes per superblock
+    constexpr int RPW = KG_BM / (2 * WN);              // rows a wave decodes per superblock
     constexpr int XP = BN * 16 / THREADS;              // 16-byte pieces of the x tile per thread (4 TN)
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint8_t *whi = smem;                               // [64][G6_LD]
-    uint8_t *wlo = whi + G6_BM * G6_LD;                // [64][G6_LD]
-    uint8_t *xs = wlo + G6_BM * G6_LD;                 // [BN][G6_LD]
-    float *dws = reinterpret_cast<float *>(xs + BN * G6_LD);   // [64]
-    float *dxs = dws + G6_BM;                          // [BN]
+    uint8_t *whi = smem;                               // [64][KG_LD]
+    uint8_t *wlo = whi + KG_BM * KG_LD;                // [64][KG_LD]
+    uint8_t *xs = wlo + KG_BM * KG_LD;                 // [BN][KG_LD]
+    float *dws = reinterpret_cast<float *>(xs + BN * KG_LD);   // [64]
+    float *dxs = dws + KG_BM;                          // [BN]
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // the column tiles of one row tile are neighbours in the grid (they share the weight rows)
     const int mt = (int)(blockIdx.x / (unsigned)ntn), nt = (int)(blockIdx.x - (unsigned)mt * (unsigned)ntn);
-    const int m0 = mt * G6_BM, n0 = nt * BN;
+    const int m0 = mt * KG_BM, n0 = nt * BN;
     const int K = nb * QK_K;
     const int64_t rowbytes = (int64_t)nb * Q6KB;
 
@@ -116,9 +102,9 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q6_K(const uint8_t *__restric
     }
     int xoff[XP];
 #pragma unroll
-    for (int i = 0; i < XP; i++) {
-        const int p = tid + THREADS * i, n = n0 + (p >> 4);
-        xoff[i] = (n < N ? n : N - 1) * K + (p & 15) * 16;             // N K < 2^31 (host check)
+    for (int ii = 0; ii < XP; ii++) {
+        const int p = tid + THREADS * ii, n = n0 + (p >> 4);
+        xoff[ii] = (n < N ? n : N - 1) * K + (p & 15) * 16;             // N K < 2^31 (host check)
     }
     const int dn = n0 + (tid & (BN - 1));
     const int dxoff = (dn < N ? dn : N - 1) * nb;
@@ -156,23 +142,23 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q6_K(const uint8_t *__restric
             dwv = lane == u ? dw : dwv;
             uint32_t hi, lo;
             q6_digits((ql & 0x0F0F0F0Fu) | ((qh & 0x03030303u) << 4), sc, hi, lo);
-            *reinterpret_cast<uint32_t *>(whi + r * G6_LD + 4 * lane) = hi;
-            *reinterpret_cast<uint32_t *>(wlo + r * G6_LD + 4 * lane) = lo;
+            *reinterpret_cast<uint32_t *>(whi + r * KG_LD + 4 * lane) = hi;
+            *reinterpret_cast<uint32_t *>(wlo + r * KG_LD + 4 * lane) = lo;
         }
         if (lane < RPW) dws[wave * RPW + lane] = h2f(dwv);
 #pragma unroll
         for (int i = 0; i < XP; i++) {
             const int p = tid + THREADS * i;
-            *reinterpret_cast<u32x4 *>(xs + (p >> 4) * G6_LD + (p & 15) * 16) = g.x[i];
+            *reinterpret_cast<u32x4 *>(xs + (p >> 4) * KG_LD + (p & 15) * 16) = g.x[i];
         }
         if (tid < BN) dxs[tid] = g.dx;
     };
 
     const int wr = wave & 1, wt = wave >> 1;
     const int c = lane & 31, h = lane >> 5;
-    const uint8_t *bh_p = whi + (32 * wr + c) * G6_LD + 16 * h;
-    const uint8_t *bl_p = wlo + (32 * wr + c) * G6_LD + 16 * h;
-    const uint8_t *a_p = xs + (32 * TN * wt + c) * G6_LD + 16 * h;
+    const uint8_t *bh_p = whi + (32 * wr + c) * KG_LD + 16 * h;
+    const uint8_t *bl_p = wlo + (32 * wr + c) * KG_LD + 16 * h;
+    const uint8_t *a_p = xs + (32 * TN * wt + c) * KG_LD + 16 * h;
     const i32x16 iz = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     float acc[TN][16];
 #pragma unroll
@@ -198,7 +184,7 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q6_K(const uint8_t *__restric
             const i32x4 bl = *reinterpret_cast<const i32x4 *>(bl_p + 32 * s);
 #pragma unroll
             for (int t = 0; t < TN; t++) {
-                const i32x4 a = *reinterpret_cast<const i32x4 *>(a_p + 32 * t * G6_LD + 32 * s);
+                const i32x4 a = *reinterpret_cast<const i32x4 *>(a_p + 32 * t * KG_LD + 32 * s);
                 H[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bh, H[t], 0, 0, 0);
                 L[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bl, L[t], 0, 0, 0);
             }
@@ -209,7 +195,7 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q6_K(const uint8_t *__restric
         for (int t = 0; t < TN; t++)
 #pragma unroll
             for (int i = 0; i < 16; i++) {
-                const int tok = 32 * TN * wt + 32 * t + (i & 3) + 8 * (i >> 2) + 4 * h;
+                const int tok = kquant_col(32 * TN * wt + 32 * t, i, h);
                 const int isum = H[t][i] * 128 + L[t][i];
                 acc[t][i] = __builtin_fmaf(dxs[tok] * dw, (float)isum, acc[t][i]);
             }
@@ -220,36 +206,25 @@ __global__ __launch_bounds__(128 * WN) void k_gemm_q6_K(const uint8_t *__restric
 #pragma unroll
         for (int t = 0; t < TN; t++)
 #pragma unroll
-            for (int i = 0; i < 16; i++) {
-                const int n = n0 + 32 * TN * wt + 32 * t + (i & 3) + 8 * (i >> 2) + 4 * h;
-                if (n < N) y[(int64_t)n * ldy + row] = acc[t][i];
+            for (int e = 0; e < 16; e++) {
+                const int n = kquant_col(n0 + 32 * TN * wt + 32 * t, e, h);
+                if (n < N) y[(int64_t)n * ldy + row] = acc[t][e];
             }
     }
 }
 
-template <int WN, int TN>
-static hipError_t launch_gemm6(const uint8_t *W, int nb, int M, const uint8_t *xqs, const float *xd, int N, float *y,
-                               int64_t ldy, hipStream_t s) {
-    constexpr int BN = 32 * WN * TN;
-    constexpr size_t lds = (size_t)(2 * G6_BM + BN) * G6_LD + (size_t)(G6_BM + BN) * 4;
-    if (const hipError_t e = raise_dynamic_lds<k_gemm_q6_K<WN, TN>>((int)lds); e != hipSuccess) return e;
-    const int64_t ntm = ((int64_t)M + G6_BM - 1) / G6_BM, ntn = ((int64_t)N + BN - 1) / BN;
-    if (ntm * ntn >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-    (void)hipGetLastError();  // report only this launch's error
-    launch_k(k_gemm_q6_K<WN, TN>, dim3((unsigned)(ntm * ntn)), dim3(128 * WN), lds, s, W, nb, M, xqs, xd, N, (int)ntn, y, ldy);
-    return hipGetLastError();
-}
-
-// y[n * ldy + m] = W[m] . x[n] on the planes quantize_q8_K_planes wrote; any K % 256 == 0, M, N >= 1
+// y[n * ldy + m] = W[m] . x[n] on the planes quantize_q8_K_planes wrote; any K % 256 == 0, M, N >= 1.  The 256-column
+// tile for every N > 128 (no fit rule).
 hipError_t gemm_q6_K(const void *W, int64_t K, int64_t M, const void *xqs, const float *xd, int64_t N, float *y,
-                     int64_t ldy, hipStream_t s) {
-    if (K <= 0 || K % QK_K || M < 1 || M >= ((int64_t)1 << 31) || N < 1 || N * K >= ((int64_t)1 << 31))
-        return hipErrorInvalidValue;
-    const int nb = (int)(K / QK_K);
-    const uint8_t *w = (const uint8_t *)W, *q = (const uint8_t *)xqs;
-    if (N <= 64) return launch_gemm6<2, 1>(w, nb, (int)M, q, xd, (int)N, y, ldy, s);
-    if (N <= 128) return launch_gemm6<4, 1>(w, nb, (int)M, q, xd, (int)N, y, ldy, s);
-    return launch_gemm6<4, 2>(w, nb, (int)M, q, xd, (int)N, y, ldy, s);
+                     int64_t ldy, const DeviceInfo &dev, hipStream_t s) {
+    return with_kquant_tile(K, M, N, dev.num_cus, false, [&](auto wn, auto tn, int nb) {
+        constexpr int WN = decltype(wn)::value, TN = decltype(tn)::value, BN = 32 * WN * TN;
+        constexpr size_t lds = (size_t)(2 * KG_BM + BN) * KG_LD + (size_t)(KG_BM + BN) * 4;
+        return launch_gemm_kquant<k_gemm_q6_K<WN, TN>, WN, TN>(lds, M, N, [&](dim3 grid, dim3 block, int ntn) {
+            launch_k(k_gemm_q6_K<WN, TN>, grid, block, lds, s, (const uint8_t *)W, nb, (int)M, (const uint8_t *)xqs, xd,
+                     (int)N, ntn, y, ldy);
+        });
+    });
 }
 
 }  // namespace ghip

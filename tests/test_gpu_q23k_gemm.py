@@ -222,6 +222,8 @@ def test_gemm_status_codes(exact_off, variant):
     assert mm(b.ptr, 384, 4, b.ptr, 1, b.ptr, 4, GEMM, None) == ggml_hip.ERR_INVALID       # K % 256
     assert mm(b.ptr, 256, 4, b.ptr, 1, b.ptr, 3, GEMM, None) == ggml_hip.ERR_INVALID       # ldy < M
     assert mm(b.ptr, 256, 4, b.ptr, 0, b.ptr, 4, GEMM, None) == ggml_hip.OK                # N = 0
+    # an algo the types reject is refused before anything else, an empty call included
+    assert mm(b.ptr, 256, 4, b.ptr, 0, b.ptr, 4, 3, None) == ggml_hip.ERR_INVALID
 
 
 # ---- 3. hook path -----------------------------------------------------------------------------------------

@@ -216,6 +216,8 @@ def test_gemm_status_codes(L):
     assert L.ggml_hip_mul_mat_q6_K(b.ptr, 256, 4, b.ptr, 1, b.ptr, 4, 3, None) == ggml_hip.ERR_INVALID
     assert L.ggml_hip_mul_mat_q6_K(b.ptr, 256, 4, b.ptr, 1, b.ptr, 3, GEMM, None) == ggml_hip.ERR_INVALID   # ldy < M
     assert L.ggml_hip_mul_mat_q6_K(b.ptr, 256, 4, b.ptr, 0, b.ptr, 4, GEMM, None) == ggml_hip.OK            # N = 0
+    # Q6_K checks the operands before the algo: an empty call is OK whatever the algo
+    assert L.ggml_hip_mul_mat_q6_K(b.ptr, 256, 4, b.ptr, 0, b.ptr, 4, 3, None) == ggml_hip.OK
 
 
 def test_reserved_workspace_covers_the_gemm(L):
