@@ -17,7 +17,11 @@
  * Q3_K" and "mostly Q2_K" files (ggml_vec_dot_q3_K_q8_K / _q2_K_q8_K semantics),
  * and with src0 = GGML_TYPE_Q4_1 / Q5_0 / Q5_1, and with src0 = a 2-D
  * GGML_TYPE_F16 leaf: the matrices of a "mostly F16" file
- * (ggml_compute_forward_mul_mat_f16_f32 semantics).
+ * (ggml_compute_forward_mul_mat_f16_f32 semantics), and with src0 = a 2-D
+ * GGML_TYPE_F32 leaf with K % 32 == 0: the matrices of an "all F32" file
+ * (ggml_compute_forward_mul_mat_f32 semantics) once an operand is on the
+ * device; an all-host F32 node only with GGML_HIP_F32_W=1 /
+ * ggml_hip_debug_set_f32_w(1) (off by default).
  * src0 = GGML_TYPE_Q4_K (a "mostly Q4_K" file) is taken on this hook path only
  * with GGML_HIP_Q4_K=1 / ggml_hip_debug_set_q4_K(1) (off by default);
  * the tensor-free ggml_hip_mul_mat_q4_K always runs.  Everything
@@ -355,6 +359,46 @@ int ggml_hip_debug_f16w_wgemm_plan(int64_t K, int64_t M, int64_t N);
  * measured rows are in DESIGN.md section 4b); values below 9 count as 9; -1 restores the environment value or the
  * default.  Returns the previous value. */
 int ggml_hip_debug_set_f16w_gemm_min_n(int n);
+/* F32 WEIGHTS (contiguous rows of K floats; dev_w 16-byte aligned, K % 32 == 0: the matrices of an "all F32" file,
+ * ftype 0) x F32 -> F32 with the semantics of ggml_compute_forward_mul_mat_f32 (ggml.c:10855): no operand is rounded,
+ * every product enters by one fmaf, fp32 subnormals are kept.  y[n * ldy + m], any ldy >= M for every algo.
+ * Stream-ordered and capturable; no workspace but algo 12's.  No byte outside [dev_w, dev_w + M * K * 4) and
+ * [dev_x, dev_x + N * K * 4) is read, and only the M columns of the N rows of y are written.  Status codes as for
+ * ggml_hip_mul_mat_f16; N == 0 is a no-op.  algo: 0 auto (4 in exact mode; else 4 for a K the GEMV cannot take; else 12
+ * when N >= the GEMM threshold; else 1), 1 GEMV (K <= 32768; column tiles of min(8, 32768 / K) columns, bitwise the
+ * per-tile calls) with one fixed order of the additions per K (csrc/f32_w.hip, restated in tests/f32w_ref.py
+ * gemv_schedule; y does not depend on N, M or the launch geometry), 4 exact: bit-identical to ggml_vec_dot_f32 in its
+ * AVX2 + FMA schedule (32 chains, GGML_F32x8_REDUCE), 12 prefill GEMM on v_mfma_f32_32x32x2_f32 (csrc/f32_w_gemm.hip):
+ * K is cut into S (1, 2 or 4) equal slices, each ONE fmaf chain per output over the slice's elements in natural order
+ * from +0, the slices' values added in slice order by a second launch (no atomics); y is bitwise
+ * tests/f32w_ref.py gemm_schedule(w, x, S) and depends on (row, column, K, S) alone, so with S pinned a column or row
+ * slice of a call is bitwise the call on that slice.  S is a pure function of K, M, N and the device's CU count unless
+ * pinned; a requested S for which K / S is no multiple of 32 runs as the next smaller one.  Algo 12 uses the stream's
+ * workspace for S > 1 (S fp32 [N][M] slabs); ggml_hip_reserve_workspace_mm(K, N, M) reserves it for the split in force
+ * at the time of the reservation, and a reserved call is capturable.  Every algo is within
+ * |y - S64| <= 1.01 * K * 2^-24 * sum |W * x| of the float64 sum S64 of the exact products.  Anything else (2, 3, 5 - 11,
+ * 13 included) -> GGML_HIP_ERR_INVALID, before anything else is checked; 1 on K > 32768 and 12 on a shape whose tiles
+ * exceed one grid -> GGML_HIP_ERR_UNSUPPORTED (auto then runs the GEMV's tiles). */
+int ggml_hip_mul_mat_f32(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N,
+                         float *dev_y, int64_t ldy, int algo, void *stream);
+/* debug, no device needed: the algo that algo 0 of ggml_hip_mul_mat_f32 would run now: 1, 4 or 12; a bad K ->
+ * GGML_HIP_ERR_INVALID */
+int ggml_hip_debug_f32w_auto_algo(int64_t K, int64_t M, int64_t N);
+/* debug: the smallest N at which auto takes the F32 GEMM (algo 12).  Default 16, the measured crossover (GGML_HIP_F32W_GEMM_MIN_N; DESIGN.md
+ * section 4b); values below 9 count as 9; -1 restores the environment value or the default.  Returns the previous
+ * value. */
+int ggml_hip_debug_set_f32w_gemm_min_n(int n);
+/* debug: pin algo 12's K split: 0 auto, 1, 2 or 4.  Returns the previous value; anything else ->
+ * GGML_HIP_ERR_INVALID. */
+int ggml_hip_debug_set_f32w_gemm_ksplit(int s);
+/* debug, no device needed: the split auto would run now for this shape (the current device's CU count; 256 where no
+ * device is initialised), whatever is pinned */
+int ggml_hip_debug_f32w_gemm_ksplit(int64_t K, int64_t M, int64_t N);
+/* The hook path takes an ALL-HOST mul_mat with an F32 weight (a contiguous 2-D F32 leaf, K % 32 == 0) only with this
+ * switch on (GGML_HIP_F32_W=1; default off, so the small F32 matrices of graphs that never offload stay on ggml's CPU
+ * op).  A matrix ggml_hip_transform_tensor uploaded, or a host one between device operands, is served regardless.
+ * Returns the previous value (0 / 1). */
+int ggml_hip_debug_set_f32_w(int on);
 
 /* Sibling mul_mats that share the activation x (ggml graphs issue wq/wk/wv and w1/w3 on the same
  * src1): n <= 4 weight matrices of the same K, y_i = W_i x with y_i f32 [N][M_i].  One launch for

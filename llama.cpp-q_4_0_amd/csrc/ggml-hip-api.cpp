@@ -246,6 +246,32 @@ int ggml_hip_debug_f16w_wgemm_plan(int64_t K, int64_t M, int64_t N) {
     return ghip::gemm_f16w_auto_plan(K, M, N, g_device_count > 0 ? g_dev[current_device()].info.num_cus : 0);
 }
 
+// F32 weights (f32_w.hip, f32_w_gemm.hip)
+int ggml_hip_mul_mat_f32(const void *dev_w, int64_t K, int64_t M, const float *dev_x, int64_t N, float *dev_y,
+                         int64_t ldy, int algo, void *stream) {
+    return mul_mat_type(gabi::TYPE_F32, dev_w, K, M, dev_x, N, dev_y, ldy, algo, stream);
+}
+
+int ggml_hip_debug_f32w_auto_algo(int64_t K, int64_t M, int64_t N) {
+    if (K <= 0 || K % 32 || M <= 0 || N < 0) return fail(GGML_HIP_ERR_INVALID, "bad shape");
+    return auto_algo_f32w(K, M, N);
+}
+
+int ggml_hip_debug_set_f32w_gemm_min_n(int n) { return weight_type(gabi::TYPE_F32)->min_n->set(n); }
+
+int ggml_hip_debug_set_f32w_gemm_ksplit(int s) {
+    if (s != 0 && s != 1 && s != 2 && s != 4) return fail(GGML_HIP_ERR_INVALID, "ksplit must be 0 (auto), 1, 2 or 4");
+    return ghip::gemm_f32w_set_ksplit(s);
+}
+
+// the split auto would run now on the current device (256 CUs where there is none); no device is initialised for it
+int ggml_hip_debug_f32w_gemm_ksplit(int64_t K, int64_t M, int64_t N) {
+    if (K <= 0 || K % 32 || M <= 0 || N < 0) return fail(GGML_HIP_ERR_INVALID, "bad shape");
+    return ghip::gemm_f32w_auto_ksplit(K, M, N, g_device_count > 0 ? g_dev[current_device()].info.num_cus : 0);
+}
+
+int ggml_hip_debug_set_f32_w(int on) { return f32w_set_enabled(on); }
+
 /* not in the public header: force the Q8_0 GEMV's launch policy (tests: every policy gives the same y bitwise) */
 int ggml_hip_debug_set_q8_0_gemv_policy(int map, int depth, int wg_per_cu) {
     ghip::gemv_q8_0w_set_policy(map, depth, wg_per_cu);
@@ -382,7 +408,8 @@ int ggml_hip_reserve_workspace_mm(int64_t K, int64_t N, int64_t M) {
     if (K <= 0 || N < 0 || M < 0) return fail(GGML_HIP_ERR_INVALID, "bad shape");
     const int id = current_device();
     return reserve_workspace(id, std::max({workspace_bytes_mm(K, N, M), workspace_bytes_q81(K, N),
-                                           workspace_bytes_f16w_gemm(id, K, N, M)}));
+                                           workspace_bytes_f16w_gemm(id, K, N, M),
+                                           K % 32 == 0 ? workspace_bytes_f32w_gemm(id, K, N, M) : (size_t)0}));
 }
 
 // ------------------------------------------------------------------------------------------

@@ -360,6 +360,11 @@ static GemmMinN g_f16w_min_n{"GGML_HIP_F16W_GEMM_MIN_N", 32};
 // profiles/f16w_wgemm.json).  Its y is within the bound of the GEMV's and of algo 9's, not bitwise either.
 static GemmMinN g_f16w_wgemm_min_n{"GGML_HIP_F16W_WGEMM_MIN_N", INT_MAX};
 GemmMinN *f16w_wgemm_min_n() { return &g_f16w_wgemm_min_n; }
+// F32 (algo 12 = k_gemm_f32w, f32_w_gemm.hip): 16, the smallest swept N from which the GEMM beats the GEMV's column
+// tiles on all three LLaMA-7B layer shapes with spreads that do not overlap (tools/f32w_bench.py, profiles/f32w.json,
+// DESIGN §4b; weights from HBM).  At N = 9 the two tie on 4096 -> 4096 and the GEMM wins the other two shapes; at
+// K = 11008, where the GEMV takes 2 columns per launch, the GEMM wins from the rule's floor of 9.
+static GemmMinN g_f32w_min_n{"GGML_HIP_F32W_GEMM_MIN_N", 16};
 
 // the K a type's GEMV takes: one token's q8_K image in the LDS for the k-quants (w2 of a 30B / 65B model has K =
 // 17920 / 22016), one token's q8_0 for Q8_0
@@ -367,11 +372,12 @@ static bool gemv_takes_k_kquant(int64_t K) { return K <= 16384; }
 static bool gemv_takes_k_q8_0(int64_t K) { return ghip::gemv_q8_0w_max_tokens(K) >= 1; }
 static bool gemv_takes_k_q5x(int64_t K) { return ghip::gemv_q5x_max_tokens(K) >= 1; }
 static bool gemv_takes_k_f16w(int64_t K) { return ghip::gemv_f16w_max_tokens(K) >= 1; }
+static bool gemv_takes_k_f32w(int64_t K) { return ghip::gemv_f32w_max_tokens(K) >= 1; }
 
 static MulMatSig mul_mat_q6k_dev, mul_mat_q8_0_dev, mul_mat_q5k_dev, mul_mat_q4k_dev;
 static MulMatSig mul_mat_q4_1_dev, mul_mat_q5_0_dev, mul_mat_q5_1_dev;
 static MulMatSig mul_mat_q3k_dev, mul_mat_q2k_dev;
-static MulMatSig mul_mat_f16w_dev;
+static MulMatSig mul_mat_f16w_dev, mul_mat_f32w_dev;
 
 static constexpr const char *ERR_K256 = "K must be a multiple of 256 (QK_K)";
 static constexpr const char *ERR_ALIGN_Q45K = "W and x must be 16-byte, y 4-byte aligned";
@@ -459,8 +465,19 @@ static const WeightType ROW_F16 = {
     "K must be a multiple of 32", "W and x must be 16-byte, y 4-byte aligned", "K too long for the F16 GEMV",
     32, 16, "F16 rows are not dequantized"};
 
+// F32 (f32_w.hip, f32_w_gemm.hip; the "all F32" files): contiguous rows of K floats, 16-byte aligned, K % 32 == 0 (the
+// scalar leftover loop of ggml_vec_dot_f32 is contracted or not at the compiler's discretion, so no exact kernel can
+// restate it).  Nothing is dequantized.  The exact kernel where the GEMV cannot take K (one column's 4 K bytes past
+// the LDS).
+static const WeightType ROW_F32 = {
+    32, 16, (int64_t)1 << 31,
+    12, 4, &g_f32w_min_n, gemv_takes_k_f32w, mul_mat_f32w_dev,
+    "K must be a multiple of 32", "W and x must be 16-byte, y 4-byte aligned", "K too long for the F32 GEMV",
+    32, 16, "F32 rows are not dequantized"};
+
 const WeightType *weight_type(int type) {
     switch (type) {
+        case gabi::TYPE_F32: return &ROW_F32;
         case gabi::TYPE_F16: return &ROW_F16;
         case gabi::TYPE_Q4_1: return &ROW_Q4_1;
         case gabi::TYPE_Q5_0: return &ROW_Q5_0;
@@ -493,6 +510,18 @@ int auto_algo_f16w(int64_t K, int64_t M, int64_t N) {
 // 256 CUs where there is no device)
 size_t workspace_bytes_f16w_gemm(int id, int64_t K, int64_t N, int64_t M) {
     return ghip::gemm_f16w_ws_bytes(K, M, N, id >= 0 && id < g_device_count ? g_dev[id].info.num_cus : 0);
+}
+
+// F32: the table's rule; the GEMM only where one launch's grid takes the shape (else the GEMV's column tiles)
+int auto_algo_f32w(int64_t K, int64_t M, int64_t N) {
+    const int algo = auto_algo(ROW_F32, K, N);
+    return algo == 12 && !ghip::gemm_f32w_supported(K, M, N) ? 1 : algo;
+}
+
+// the workspace of algo 12 (the K-slice slabs of the split the call would run now on device id; 256 CUs where there
+// is no device)
+size_t workspace_bytes_f32w_gemm(int id, int64_t K, int64_t N, int64_t M) {
+    return ghip::gemm_f32w_ws_bytes(K, M, N, id >= 0 && id < g_device_count ? g_dev[id].info.num_cus : 0);
 }
 
 // OK with N == 0 means there is nothing to run: the steps behind it are not checked then
@@ -702,6 +731,40 @@ static int mul_mat_f16w_dev(const void *w, int64_t K, int64_t M, const float *x,
     return GGML_HIP_OK;
 }
 
+// F32 (f32_w.hip, f32_w_gemm.hip): algo 1 = k_gemv_f32w in column tiles, algo 4 = k_mm_exact_f32w (ggml_vec_dot_f32's
+// AVX2 schedule, bitwise), algo 12 = k_gemm_f32w on v_mfma_f32_32x32x2_f32 with its K-slice slabs in the workspace.
+// Every algo takes any ldy >= M.  An algo the type rejects is refused before anything else, an empty call included.
+static int mul_mat_f32w_dev(const void *w, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, int algo,
+                            hipStream_t s) {
+    if (algo != 0 && algo != 1 && algo != 4 && algo != 12) return fail(GGML_HIP_ERR_INVALID, "algo must be 0, 1, 4 or 12");
+    const WeightType &t = ROW_F32;
+    const int rc = check_operands(t, w, K, M, x, N, y, ldy);
+    if (rc != GGML_HIP_OK || N == 0) return rc;
+    const int id = current_device();
+    if (algo == 0) algo = auto_algo_f32w(K, M, N);
+    if (algo == 1) {
+        if (!t.gemv_takes_k(K)) return fail(GGML_HIP_ERR_UNSUPPORTED, t.err_gemv_k);
+        HIP_RET(ghip::gemv_f32w(w, K, M, x, N, y, ldy, g_dev[id].info, s));
+        return GGML_HIP_OK;
+    }
+    if (algo == 12) {
+        if (!ghip::gemm_f32w_supported(K, M, N))
+            return fail(GGML_HIP_ERR_UNSUPPORTED, "too many tiles for one grid of the F32 GEMM (algo 12); split rows or columns");
+        void *ws = nullptr;
+        const size_t need = workspace_bytes_f32w_gemm(id, K, N, M);
+        if (need) {
+            const int wrc = stream_workspace(id, s, need, &ws);
+            if (wrc != GGML_HIP_OK) return wrc;
+        }
+        HIP_RET(ghip::gemm_f32w(w, K, M, x, N, y, ldy, ws, need, g_dev[id].info, s));
+        return GGML_HIP_OK;
+    }
+    if (N * M * 32 / 256 + 1 >= ((int64_t)1 << 31))
+        return fail(GGML_HIP_ERR_UNSUPPORTED, "too many outputs for one grid of the exact F32 kernel; split rows or columns");
+    HIP_RET(ghip::mm_exact_f32w(w, K, M, x, N, y, ldy, s));
+    return GGML_HIP_OK;
+}
+
 // Sibling matrices (one x) that all take k_gemm9 on a registered fp6 image: ONE launch over their
 // row tiles (the x image built once, as before).  The launch plans its tiles (128 x 128 / 128 x 64 /
 // mixed, half tiles) from its own total tile count, which can differ from the per-matrix launches'
@@ -810,7 +873,32 @@ bool f16_weight(const tensor *t) {
     return t && t->type == gabi::TYPE_F16 && t->op == gabi::OP_NONE && t->ne[2] == 1 && t->ne[3] == 1 && t->ne[0] > 0 &&
            t->ne[0] % ROW_F16.k_granule == 0 && is_contiguous(t);
 }
+// F32 weights: a contiguous 2-D F32 leaf with K % 32 == 0.  All-host F32 mul_mats are taken only with this switch on
+// (GGML_HIP_F32_W=1 / ggml_hip_debug_set_f32_w; default off: the small F32 matrices of the arch frontends stay on
+// ggml's CPU op); a matrix transform_tensor uploaded, or a host one between device operands, is served regardless,
+// like Q4_K with its switch off.
+std::atomic<int> g_f32w{-1};
+bool f32w_enabled() {
+    int v = g_f32w.load(std::memory_order_relaxed);
+    if (v < 0) {
+        const char *e = getenv("GGML_HIP_F32_W");
+        int want = (e && atoi(e) != 0) ? 1 : 0, expect = -1;
+        g_f32w.compare_exchange_strong(expect, want);
+        v = g_f32w.load(std::memory_order_relaxed);
+    }
+    return v != 0;
+}
+int f32w_set_enabled(int on) {
+    const int prev = f32w_enabled() ? 1 : 0;
+    g_f32w.store(on ? 1 : 0, std::memory_order_relaxed);
+    return prev;
+}
+bool f32_weight(const tensor *t) {
+    return t && t->type == gabi::TYPE_F32 && t->op == gabi::OP_NONE && t->ne[2] == 1 && t->ne[3] == 1 && t->ne[0] > 0 &&
+           t->ne[0] % ROW_F32.k_granule == 0 && is_contiguous(t);
+}
 bool hook_takes_type(int type) {
+    if (type == gabi::TYPE_F32) return f32w_enabled();
     return type == gabi::TYPE_Q4_0 || (weight_type(type) && (type != gabi::TYPE_Q4_K || q4k_enabled()));
 }
 int hook_weight_type(const tensor *src0, const tensor *src1, const tensor *dst) {
@@ -819,6 +907,10 @@ int hook_weight_type(const tensor *src0, const tensor *src1, const tensor *dst) 
     // an F16 src0 is a weight only as a 2-D leaf: the K and V views of the attention (permuted, transposed, 3-D, never
     // leaves) keep the F16 x F32 device op and its fusions
     if (src0->type == gabi::TYPE_F16 && !f16_weight(src0)) return gabi::TYPE_COUNT;
+    // an F32 src0 likewise (an F32 KV cache's views, activations); off the switch an all-host node is ggml's
+    if (src0->type == gabi::TYPE_F32 &&
+        (!f32_weight(src0) || (!f32w_enabled() && !(on_device(src0) && src0->extra) && !on_device(src1) && !on_device(dst))))
+        return gabi::TYPE_COUNT;
     if (src0->type == gabi::TYPE_Q4_K && !q4k_enabled() && !(on_device(src0) && src0->extra) && !on_device(src1) &&
         !on_device(dst))
         return gabi::TYPE_COUNT;

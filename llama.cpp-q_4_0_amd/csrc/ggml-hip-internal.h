@@ -195,6 +195,9 @@ int auto_algo(const WeightType &t, int64_t K, int64_t N);   // what algo 0 runs 
 int auto_algo_f16w(int64_t K, int64_t M, int64_t N);
 GemmMinN *f16w_wgemm_min_n();
 size_t workspace_bytes_f16w_gemm(int id, int64_t K, int64_t N, int64_t M);
+// F32: the table's rule where the GEMM's launch takes the shape; the workspace of its K-slice slabs
+int auto_algo_f32w(int64_t K, int64_t M, int64_t N);
+size_t workspace_bytes_f32w_gemm(int id, int64_t K, int64_t N, int64_t M);
 int check_operands(const WeightType &t, const void *w, int64_t K, int64_t M, const float *x, int64_t N, const float *y,
                    int64_t ldy);
 // the hook path takes Q4_K tensors only with this switch on (GGML_HIP_Q4_K=1 / ggml_hip_debug_set_q4_K; default off);
@@ -206,6 +209,11 @@ int q4k_set_enabled(int on);                            // returns the previous 
 bool hook_takes_type(int type);
 // an F16 tensor that is a weight matrix: a contiguous 2-D leaf with K % 32 == 0 (every other F16 src0 is the attention's)
 bool f16_weight(const tensor *t);
+// an F32 tensor that is a weight matrix: a contiguous 2-D leaf with K % 32 == 0; all-host F32 nodes are taken only with
+// the switch on (GGML_HIP_F32_W=1 / ggml_hip_debug_set_f32_w; default off)
+bool f32_weight(const tensor *t);
+bool f32w_enabled();
+int f32w_set_enabled(int on);                           // returns the previous value (0 / 1)
 int hook_weight_type(const tensor *src0, const tensor *src1, const tensor *dst);
 // true when ggml_hip_mul_mat_q4_0_multi runs these n siblings at N tokens as ONE k_gemm9 launch on registered
 // fp6 images (mul_mat_group_g9 for n > 1, mul_mat_dev's image GEMM for n = 1); img[i] = the images

@@ -158,7 +158,7 @@ void mul_mat_node(const tensor *src0, const tensor *src1, tensor *dst) {
     if (wtype == gabi::TYPE_COUNT) {
         fprintf(stderr, "ggml_hip_mul_mat: unsupported operands (need contiguous Q4_0, Q4_1, Q5_0, Q5_1 or Q8_0 x F32 -> F32, "
                         "K %% 64 == 0, or Q6_K, Q5_K, Q3_K, Q2_K (Q4_K with GGML_HIP_Q4_K=1) x F32 -> F32, K %% 256 == 0, or a "
-                        "2-D F16 leaf x F32 -> F32, K %% 32 == 0)\n");
+                        "2-D F16 or F32 leaf x F32 -> F32, K %% 32 == 0; an all-host F32 node with GGML_HIP_F32_W=1)\n");
         abort();
     }
     const int64_t K = src0->ne[0], M = src0->ne[1], N = src1->ne[1];
@@ -371,7 +371,10 @@ void ggml_hip_transform_tensor(void *data, struct ggml_tensor *tensor_) {
     }
     // only the weight mul_mats read row-split operands: the quantized types and F16 matrices (f16_weight: the
     // F16 x F32 device op of every other F16 tensor reads one device buffer)
-    if (t->backend == gabi::BACKEND_GPU_SPLIT && (t->type == gabi::TYPE_F16 ? !f16_weight(t) : !hook_takes_type(t->type)))
+    // (f32_weight likewise: every other F32 tensor, the 2-D ones with K % 32 != 0 included, is one device buffer)
+    if (t->backend == gabi::BACKEND_GPU_SPLIT && (t->type == gabi::TYPE_F16   ? !f16_weight(t)
+                                                  : t->type == gabi::TYPE_F32 ? !f32_weight(t)
+                                                                              : !hook_takes_type(t->type)))
         t->backend = gabi::BACKEND_GPU;
     const int64_t nrows = gabi::nrows(t);
     const size_t nb1 = t->nb[1];

@@ -256,6 +256,29 @@ size_t gemm_f16w_ws_bytes(int64_t K, int64_t M, int64_t N, int num_cus);
 hipError_t gemm_f16w(const void *W, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, void *ws,
                      size_t ws_bytes, const DeviceInfo &dev, hipStream_t s);
 
+// ---- F32 weights (f32_w.hip): y[n * ldy + m] = sum_e W[m][e] * x[n][e], W contiguous F32 rows (16-byte aligned,
+// K % 32 == 0), fmaf on the unrounded operands, one fixed order per K (tests/f32w_ref.py gemv_schedule).  N >
+// gemv_f32w_max_tokens(K) runs column tiles (a column's y does not depend on its tile); max_tokens is 8 up to K = 4096,
+// 2 at K = 11008 and 0 where one column's floats exceed the LDS (K > 32768).  mm_exact: ggml_vec_dot_f32's AVX2
+// schedule bit for bit, any N, ldy >= M.
+int gemv_f32w_max_tokens(int64_t K);
+hipError_t gemv_f32w(const void *W, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
+                     const DeviceInfo &dev, hipStream_t s);
+hipError_t mm_exact_f32w(const void *W, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy,
+                         hipStream_t s);
+// prefill (f32_w_gemm.hip): the f32-MFMA GEMM, any K % 32 == 0 (N K < 2^31), M, N >= 1, ldy >= M; y is one fmaf chain
+// per K slice in natural order and the slices added in order, a function of K and the split S alone.  S (1, 2, 4) is a
+// pure function of (K, M, N, CU count; 256 CUs where num_cus <= 0) unless one is pinned (set_ksplit: 0 auto, returns
+// the previous); a pinned S that leaves no whole 32-element chunks per slice runs as the next smaller one (ksplit
+// returns what runs).  ws: ws_bytes(K, M, N, num_cus) bytes for the slabs.
+int gemm_f32w_ksplit(int64_t K, int64_t M, int64_t N, int num_cus);      // the pinned split, or auto's
+int gemm_f32w_auto_ksplit(int64_t K, int64_t M, int64_t N, int num_cus);
+int gemm_f32w_set_ksplit(int s);
+bool gemm_f32w_supported(int64_t K, int64_t M, int64_t N);
+size_t gemm_f32w_ws_bytes(int64_t K, int64_t M, int64_t N, int num_cus);
+hipError_t gemm_f32w(const void *W, int64_t K, int64_t M, const float *x, int64_t N, float *y, int64_t ldy, void *ws,
+                     size_t ws_bytes, const DeviceInfo &dev, hipStream_t s);
+
 // Multi-GPU helper: y[n*ldy + row0[r] + i] = slab[r][n][i] for i < rows[r] (gather compaction).
 // row_begin travels as a kernel argument (no host->device copy, capture-safe)
 static constexpr int SCATTER_MAX_RANKS = 256;

@@ -96,6 +96,12 @@ def _bind(L):
         "ggml_hip_debug_set_f16w_wgemm_min_n": ([i32], i32),
         "ggml_hip_debug_set_f16w_wgemm_plan": ([i32], i32),
         "ggml_hip_debug_f16w_wgemm_plan": ([i64, i64, i64], i32),
+        "ggml_hip_mul_mat_f32": ([vp, i64, i64, vp, i64, vp, i64, i32, vp], i32),
+        "ggml_hip_debug_f32w_auto_algo": ([i64, i64, i64], i32),
+        "ggml_hip_debug_set_f32w_gemm_min_n": ([i32], i32),
+        "ggml_hip_debug_set_f32w_gemm_ksplit": ([i32], i32),
+        "ggml_hip_debug_f32w_gemm_ksplit": ([i64, i64, i64], i32),
+        "ggml_hip_debug_set_f32_w": ([i32], i32),
         "ggml_hip_reserve_workspace": ([i64, i64], i32),
         "ggml_hip_reserve_workspace_mm": ([i64, i64, i64], i32),
         "ggml_hip_weight_image_create": ([vp, i64, i64, vp], i32),
@@ -360,6 +366,13 @@ def mul_mat_f16(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_o
     threshold: 9; else 1), 1 GEMV (column tiles), 4 exact and 9 f16-MFMA GEMM (the attention's F16 x F32 kernels; ldy
     == M only), 11 the f16-MFMA GEMM decomposed for weight shapes (any ldy >= M; the stream's workspace)."""
     _mul_mat_typed("mul_mat_f16", w_dev, K, M, x_dev, N, y_dev, algo, ldy, stream, w_off, x_off, y_off)
+
+
+def mul_mat_f32(w_dev, K, M, x_dev, N, y_dev, algo=0, ldy=None, stream=None, w_off=0, x_off=0, y_off=0):
+    """F32 rows (4 * K bytes each, 16-byte aligned, K % 32 == 0) x f32 [N][K] -> f32 y[n * ldy + m], any ldy >= M; algo 0
+    auto (exact mode, or K too long for the GEMV: 4; N from the GEMM threshold: 12; else 1), 1 GEMV (column tiles),
+    4 exact (ggml_vec_dot_f32's AVX2 schedule), 12 the f32-MFMA GEMM (K split 1 / 2 / 4; the stream's workspace)."""
+    _mul_mat_typed("mul_mat_f32", w_dev, K, M, x_dev, N, y_dev, algo, ldy, stream, w_off, x_off, y_off)
 
 
 def dequantize_q5_K(wq_dev, K, M, w_dev, stream=None):
